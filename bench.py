@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """PCApply throughput of the MI355X circulant FFT preconditioner.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 256] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it builds the plan, runs the W warm-up steps and
+the settle phase, times the K steps, writes the outputs of the last timed step when
+--dump-outputs is given, and prints one JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  Everything under "Also reported" below runs with --full only.
+
+--dump-outputs DIR writes x of the last timed apply as DIR/x.npy (float64, shape (M, 2) = re, im;
+N > 1: DIR/x_rank<r>.npy, this rank's slab).  Up to DUMP_MAX_BYTES in all the whole vector is
+written; a larger one is sampled at M fixed positions drawn once from numpy's default_rng(SEED),
+in ascending order, so two runs with the same arguments write the same positions of the same
+inputs.
 
 One "step" = one PCApply x = (1/N) IDFT3(DFT3(b) ./ Diag) over one synthetic
 256^3 complex-double grid (BASELINE.json metric "PCApply/s on 256^3 complex
@@ -13,7 +24,9 @@ torch.distributed.run, one rank per GPU): the same grid slab-decomposed along
 z over N GPUs with two RCCL all-to-all transposes per apply (strong scaling;
 value = whole-job PCApply/s).
 
-Also reported: the roofline of the dominant kernel (algorithmic
+Also reported with --full: the output check of the last timed apply (a failed
+check exits with status 3), the real-data variant, the other BASELINE configs, the 512^3
+scaling item, the roofline of the dominant kernel (algorithmic
 bytes / its mean duration from HIP events on the launch stream, vs 8 TB/s), the
 apply-level roofline on the bytes the schedule moves (frac_moved; SURVEY's
 B_alg = 208 N figure beside it as a speedup, not a fraction), and a CPU
@@ -36,7 +49,31 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, spec)
 LAM = (0.6, 0.15, 0.02)  # lambda set A, testFftSolver_3D.py:85-91
 SEED = 20251017
 RES_TOL = 1e-10  # north_star's parity bar, applied to the residual of the timed applies
+DUMP_MAX_BYTES = 32 << 20  # --dump-outputs: bytes written per run (all ranks together)
 
+
+def dump_sample_index(n: int, max_bytes: int):
+    """Positions of an n-element c128 vector that --dump-outputs writes within max_bytes (16 bytes
+    each): None = all of them, else a sorted int64 array drawn from default_rng(SEED)."""
+    import numpy as np
+    m = max(1, max_bytes // 16)
+    if n <= m:
+        return None
+    return np.sort(np.random.default_rng(SEED).integers(0, n, size=m, dtype=np.int64))
+
+
+def dump_outputs(dirname: str, x, rank: int = 0, world: int = 1) -> str:
+    """Write the c128 device vector x (one GPU: the whole output; N > 1: this rank's slab) as
+    float64 (re, im) pairs to DIR/x.npy (DIR/x_rank<r>.npy)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_sample_index(x.numel(), DUMP_MAX_BYTES // world)
+    v = x if idx is None else x[torch.from_numpy(idx).to(x.device)]
+    a = np.ascontiguousarray(torch.view_as_real(v).cpu().numpy(), dtype=np.float64)
+    path = os.path.join(dirname, "x.npy" if world == 1 else f"x_rank{rank}.npy")
+    np.save(path, a)
+    return path
 
 
 def transport_residual(b, x, g, lam, rank: int = 0, world: int = 1, dev=None) -> float:
@@ -80,7 +117,7 @@ def log(*a):
 
 # Per-phase deadlines (seconds).  "timed" and "scaling_512" grow with the step count.
 DEADLINES = {"import": 900.0, "init": 300.0, "plan": 360.0, "first_apply": 120.0, "settle": 120.0,
-             "timed": 120.0, "check": 120.0, "real": 180.0, "configs": 300.0, "scaling_512": 420.0,
+             "timed": 120.0, "dump": 120.0, "check": 120.0, "real": 180.0, "configs": 300.0, "scaling_512": 420.0,
              "cpu_baseline": 300.0, "report": 60.0, "teardown": 120.0}
 
 
@@ -507,6 +544,13 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--grid", type=int, nargs="+", default=[256])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the output check, the per-launch timing and "
+                         "rooflines, the real-data variant, the other BASELINE configs, the 512^3 scaling "
+                         "item and the CPU baseline (a plain run only times the headline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write x of the last timed apply to DIR/x.npy (float64 re/im pairs; a fixed seeded "
+                         "sample when it exceeds DUMP_MAX_BYTES; N > 1: DIR/x_rank<r>.npy per rank)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--schedule", default="auto", choices=["auto", "five", "five_y", "three", "plane"],
                     help="apply schedule: 5 axis passes fused on z or y, 3 sweeps (256^3), or plane "
@@ -551,6 +595,11 @@ def main() -> int:
     grid = args.grid * 3 if len(args.grid) == 1 else args.grid
     if len(grid) != 3:
         raise SystemExit("--grid takes 1 or 3 integers")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps takes a positive and --warmup a non-negative number of applies")
+    if not args.full:  # a plain run times the headline only: none of the line items after it
+        args.no_real = args.no_configs = args.no_cpu_baseline = True
+        args.scaling_grid = [0]
     deadlines = parse_deadlines(args.deadline)
     if args.rccl_blocking:  # before the library loads; self-launched ranks inherit it
         os.environ["CFP_RCCL_BLOCKING"] = "1"
@@ -710,12 +759,13 @@ def main() -> int:
     timed_region_ms = None
     live_applies = 0
     every = max(1, args.event_every)
-    if world > 1 and not args.no_live_events and plan.exchange == "rccl":
+    live_events = args.full and not args.no_live_events  # a plain run records no per-launch events
+    if world > 1 and live_events and plan.exchange == "rccl":
         # the slab plan's phases (passes and RCCL exchanges) timed inside the timed applies
         plan.profile_begin((args.steps + every - 1) // every, every)
         elapsed = timed(run, args.steps, 0)
         timed_region_ms, live_applies = plan.profile_end()
-    elif world == 1 and not args.no_live_events:
+    elif world == 1 and live_events:
         # per-launch HIP events recorded by the plan inside the timed applies themselves (on
         # the launch stream), in every EVERY-th apply: the roofline's kernel time comes from
         # the timed region, and the events' own cost (~3 us each) stays out of `value`
@@ -728,13 +778,21 @@ def main() -> int:
     ms_per_step = elapsed / args.steps * 1e3
     value = args.steps / elapsed  # whole-job PCApply/s (one grid per step)
     torch.cuda.synchronize()
+    dumped = None
+    if args.dump_outputs:
+        wd.phase("dump")
+        dumped = dump_outputs(args.dump_outputs, x, rank, world)
     wd.phase("check")
-    res = residual(b, x, grid)
-    check = {"residual": res, "tol": RES_TOL, "ok": res < RES_TOL,
-             "what": "||C x - b|| / ||b|| of the last timed apply (transport circulant C, on the GPU)"}
+    check = {"ok": None, "what": "not run: --full checks the last timed apply"}
+    if args.full:
+        res = residual(b, x, grid)
+        check = {"residual": res, "tol": RES_TOL, "ok": res < RES_TOL,
+                 "what": "||C x - b|| / ||b|| of the last timed apply (transport circulant C, on the GPU)"}
 
     # per-launch timing of the dominant kernel (HIP events on the launch stream)
-    if world == 1:
+    if not args.full:
+        pass
+    elif world == 1:
         passes_info = plan.passes()
         if timed_region_ms is not None:
             ms = timed_region_ms
@@ -990,6 +1048,8 @@ def main() -> int:
             "config": {"workload": f"{nx}x{ny}x{nz} c128 circulant PCApply, transport symbol lambda={LAM}",
                        "grid": grid, "global_batch": 1, "parallelism": parallelism},
             "status": "ok",
+            "full": bool(args.full),
+            "outputs": dumped,
             "launcher": launcher,
             "exchange": exchange_used[0],
             "rccl": rccl,
@@ -1020,7 +1080,7 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     wd.stop()
-    if not check["ok"]:
+    if args.full and not check["ok"]:
         log(f"bench: output check FAILED: {check}")
         return 3
     return 0

@@ -230,6 +230,41 @@ def test_deadline_override_parsing():
         bench.parse_deadlines(["nosuchphase=3"])
 
 
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: a vector within the byte limit is written whole; a larger one at positions
+    that are sorted, in range, within the limit and the same from call to call."""
+    import numpy as np
+    assert bench.dump_sample_index(1000, 16 * 1000) is None
+    n = 256 ** 3
+    idx = bench.dump_sample_index(n, bench.DUMP_MAX_BYTES)
+    assert idx.dtype == np.int64 and 16 * idx.size <= bench.DUMP_MAX_BYTES <= 64 << 20
+    assert idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) >= 0)
+    assert idx[-1] - idx[0] > 0.99 * n  # spread over the whole vector
+    np.testing.assert_array_equal(idx, bench.dump_sample_index(n, bench.DUMP_MAX_BYTES))
+
+
+def test_dump_outputs_writes_float64_pairs(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    x = torch.arange(4096, dtype=torch.float64) * (1 - 2j)
+    p = bench.dump_outputs(str(tmp_path / "a"), x)
+    a = np.load(p)
+    assert os.path.basename(p) == "x.npy" and a.dtype == np.float64 and a.shape == (4096, 2)
+    np.testing.assert_array_equal(a[:, 0], np.arange(4096.0))
+    np.testing.assert_array_equal(a[:, 1], -2 * np.arange(4096.0))
+    # above the limit: the sampled positions; a rank of two gets half of the limit
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 * 512)
+    a = np.load(bench.dump_outputs(str(tmp_path / "b"), x, rank=1, world=2))
+    idx = bench.dump_sample_index(4096, 16 * 256)
+    assert sorted(os.listdir(tmp_path / "b")) == ["x_rank1.npy"] and a.shape == (256, 2)
+    np.testing.assert_array_equal(a[:, 0], idx.astype(np.float64))
+
+
+def test_steps_must_be_positive():
+    rc, lines, err = _bench(["--gpus", "1", "--selftest-cpu", "--steps", "0"])
+    assert rc != 0 and not lines and "--steps" in err
+
+
 def test_rccl_library_is_reported_host_only():
     """The library reports which librccl its RCCL calls bind to (torch bundles one with the same
     soname as /opt/rocm's), without a GPU."""

@@ -6,7 +6,7 @@ set -e
 TAG=${1:-r03h}
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
-B="bench.py --steps 200 --warmup 10 --no-real --scaling-grid 0 --no-cpu-baseline"
+B="bench.py --full --steps 200 --warmup 10 --no-real --scaling-grid 0 --no-cpu-baseline"
 for rep in 1 2; do
   for shape in 0,default 64,swap64pf 64,default; do
     s=${shape/,/_}

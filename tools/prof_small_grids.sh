@@ -7,7 +7,7 @@ set -e
 TAG=${1:-r03g}
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
-B="bench.py --steps 200 --warmup 10 --no-real --scaling-grid 0 --no-cpu-baseline"
+B="bench.py --full --steps 200 --warmup 10 --no-real --scaling-grid 0 --no-cpu-baseline"
 for g in 128 100; do
   timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace$g -- python $B --grid $g \
     > $OUT/${TAG}_bench$g.json 2> $OUT/${TAG}_bench$g.err

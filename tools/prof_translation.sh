@@ -7,7 +7,7 @@ set -e
 TAG=${1:-r03n}
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
-B="bench.py --grid 512 --steps 6 --warmup 2 --no-real --scaling-grid 0 --no-cpu-baseline --settle-ms 0"
+B="bench.py --full --grid 512 --steps 6 --warmup 2 --no-real --scaling-grid 0 --no-cpu-baseline --settle-ms 0"
 timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python $B \
   > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_trace.err
 timeout -s KILL 90 rocprofv3 --pmc TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum \
