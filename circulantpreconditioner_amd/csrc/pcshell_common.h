@@ -1,6 +1,9 @@
-// pcshell_common.h -- helpers shared by the PCSHELL implementations (pcshell_fft3d.cpp,
-// wave_system.cpp): cfp error -> PETSc error, and device views of Vecs (device arrays used in
-// place, host arrays staged through a temporary device buffer).
+// pcshell_common.h -- helpers shared by the PCSHELL implementations (pcshell_boundary.cpp,
+// pcshell_fft3d.cpp, pcshell_fft3d_real.cpp, wave_system.cpp): cfp error -> PETSc error, device
+// views of Vecs (device arrays used in place, host arrays staged through a temporary device
+// buffer), slab plans on a communicator, and -- for the transport PCSHELL only -- the part of an
+// FFT matrix that both scalar builds share and the interface between the scalar-independent
+// boundary (pcshell_boundary.cpp) and the scalar build behind it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +13,8 @@
 #include "../../include/circulant_fft.h"
 #include "../../include/circulant_fft_dist.h"
 #include "../../include/petsc_mini.h"
+
+struct FFTPrecTransportContext;  // include/pcshell_fft3d.h
 
 namespace cfp_pc {
 
@@ -35,6 +40,12 @@ inline void device_stream(void** st, bool* wait) {
   *wait = false;
 #endif
 }
+// that stream and the final wait, looked up where an apply starts
+struct Stream {
+  void* st = nullptr;
+  bool wait = true;
+  Stream() { device_stream(&st, &wait); }
+};
 
 // Device view of a Vec for the duration of one solve: device arrays are used in place,
 // host arrays are staged through a temporary device buffer (PCIe-inclusive path).
@@ -184,6 +195,92 @@ inline PetscErrorCode check_size(Vec v, PetscInt n, const char* name) {
   PetscInt m;
   PetscCall(VecGetLocalSize(v, &m));
   PetscCheck(m == n, PETSC_COMM_SELF, PETSC_ERR_ARG_SIZ, name);
+  return PETSC_SUCCESS;
+}
+
+// ------------------------------------------------------------------ the transport FFT matrix
+// What the MATSHELL context of both scalar builds holds (FFTShell of pcshell_fft3d.cpp, RShell of
+// pcshell_fft3d_real.cpp derive from it): the grid, the plan behind it and the bookkeeping that
+// decides whether a Diag still is the plan's own symbol.  Hidden, like everything below: a process
+// may hold both libraries, and neither may bind to (or export) the other's.
+#define CFP_INTERNAL __attribute__((visibility("hidden")))
+struct CFP_INTERNAL ShellBase {
+  int magic;                     // the build's kShellMagic while the matrix lives
+  PetscInt dims[3] = {1, 1, 1};  // n_x, n_y, n_z
+  int nranks = 1, rank = 0;
+  cfp_plan_t plan = nullptr;     // one rank: the complex plan
+  SlabBacking slab;              // several ranks: this rank's z slab (slab.plan) and its communicator
+  PetscInt z0 = 0, nzl = 1, nl = 1;  // this rank's z-planes [z0, z0 + nzl) and grid values (one rank: all)
+  uint64_t dist_version = 0;     // symbol version of slab.plan (its setters are called by its shell only)
+  bool has_lam = false;
+  uint64_t lam_version = 0;      // the symbol version right after the shell's lam was set
+  // the Diag setupFFTPrec3D materialised from the plan's symbol of version diag_version: its
+  // object id and its state right after that write (0 id: none).  The version is the plan's
+  // own counter (cfp_plan_symbol_version), so a symbol set on the plan directly through
+  // MatFFTHIPGetPlan also invalidates the fast path.
+  PetscObjectId diag_id = 0;
+  PetscObjectState diag_state = 0;
+  uint64_t diag_version = 0;
+  PetscInt solves_own = 0, solves_diag = 0;  // solve_3D calls per path (MatFFTHIPGetSolveCounts)
+
+  explicit ShellBase(int m) : magic(m) {}
+  uint64_t symbol_version() const {
+    if (slab.plan) return dist_version;
+    uint64_t v = 0;
+    cfp_plan_symbol_version(plan, &v);
+    return v;
+  }
+  // Diag holds exactly the plan's current symbol (materialised by setupFFTPrec3D, untouched since)
+  PetscErrorCode diag_is_own_symbol(Vec Diag, bool* own) const {
+    *own = false;
+    if (!diag_id || diag_version != symbol_version()) return PETSC_SUCCESS;
+    PetscObjectId id;
+    PetscObjectState st;
+    PetscCall(PetscObjectGetId((PetscObject)Diag, &id));
+    PetscCall(PetscObjectStateGet((PetscObject)Diag, &st));
+    *own = id == diag_id && st == diag_state;
+    return PETSC_SUCCESS;
+  }
+  // remember which object and state hold the symbol (solve_3D's register-symbol fast path)
+  PetscErrorCode remember_diag(Vec Diag) {
+    PetscCall(PetscObjectGetId((PetscObject)Diag, &diag_id));
+    PetscCall(PetscObjectStateGet((PetscObject)Diag, &diag_state));
+    diag_version = symbol_version();
+    return PETSC_SUCCESS;
+  }
+};
+
+// ---- pcshell_boundary.cpp <-> the scalar build linked beside it
+// defined by the scalar build: two constants and two functions, one definition per library
+extern CFP_INTERNAL const int kShellMagic;  // "FFTH" / "RFFT"
+// the plan apply is the whole PCApply when no remap surrounds it (the stand-in KSP then times a
+// PCApply by the plan's first and last kernel; otherwise by its own events)
+extern CFP_INTERNAL const bool kPlanApplyIsWholePCApply;
+// X = C^{-1} src with ctx's FFT_MAT and Diag (X may be src).  pc: the PC whose pending dots
+// request (PCMiniApplyDots) may ride in the apply, NULL when X is not the PCApply's result.
+CFP_INTERNAL PetscErrorCode pc_solve(PC pc, FFTPrecTransportContext* ctx, Vec X, Vec src);
+// y = B A x as one fused apply, where the build has one and this PC, A and x allow it (no remaps,
+// x != y: checked by the caller); *taken says whether y was written
+CFP_INTERNAL PetscErrorCode pc_fused_ba(PC pc, FFTPrecTransportContext* ctx, Mat A, Vec x, Vec y, bool* taken);
+
+// defined by pcshell_boundary.cpp
+CFP_INTERNAL PetscErrorCode shell_base(Mat A, ShellBase** out);  // the context of an FFT matrix of this build
+CFP_INTERNAL Mat ctx_remap_back(const FFTPrecTransportContext* ctx);
+// MatCreateFFTHIP in two steps, the build's own sizes and plans in between.  shell_create_plan:
+// argument checks, rank and size, dims (row-major {n_z, n_y, n_x} in), then the single-GPU plan or
+// this rank's z slab (needs nranks | n_z; n_y is split in FFTW-MPI's blocks of ceil(n_y / nranks)
+// rows, any n_y); on failure nothing is left behind but *s.  shell_create_mat: the MATSHELL.
+CFP_INTERNAL PetscErrorCode shell_create_plan(ShellBase* s, MPI_Comm comm, PetscInt ndim, const PetscInt dims[], Mat* A);
+typedef PetscErrorCode (*ShellMult)(Mat, Vec, Vec);
+CFP_INTERNAL PetscErrorCode shell_create_mat(ShellBase* s, MPI_Comm comm, PetscInt m, PetscInt n, PetscInt M, PetscInt N,
+                                             ShellMult mult, ShellMult mult_transpose, PetscErrorCode (*destroy)(Mat),
+                                             Mat* A);
+
+template <class S>
+PetscErrorCode shell_of(Mat A, S** out) {
+  ShellBase* b;
+  PetscCall(shell_base(A, &b));
+  *out = static_cast<S*>(b);
   return PETSC_SUCCESS;
 }
 

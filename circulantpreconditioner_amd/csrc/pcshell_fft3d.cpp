@@ -25,8 +25,6 @@
 #include <cmath>
 #include <complex>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/circulant_fft.h"
@@ -37,98 +35,51 @@
 namespace {
 using namespace cfp_pc;
 
-// cfp_plan.hip (internal): stop the current PCApply's dispatch stamping (cfp::g_apply_stamp)
-extern "C" void cfp_apply_stamp_clear(void);
-
-const int kFFTMagic = 0x46465448;  // "FFTH"
-
-struct FFTShell {
-  int magic = kFFTMagic;
-  cfp_plan_t plan = nullptr;        // one rank
-  cfp_dist_plan_t dplan = nullptr;  // several ranks: this rank's z slab
-  SlabBacking slab;                 // several ranks: dplan's communicator (pcshell_common.h)
-  MPI_Comm comm = PETSC_COMM_SELF;
-  int nranks = 1, rank = 0;
-  PetscInt nlocal = 0;              // this rank's rows (= N on one rank)
-  uint64_t dist_version = 0;        // symbol version of dplan (its setters are called here only)
-  // the explicit Diag last moved into dplan's z-pencil layout (0 id: none)
+struct FFTShell : ShellBase {
+  FFTShell() : ShellBase(kShellMagic) {}
+  // the explicit Diag last moved into slab.plan's z-pencil layout (0 id: none)
   PetscObjectId dt_id = 0;
   PetscObjectState dt_state = 0;
-  void* stage = nullptr;            // in-place host-Vec staging of the slab path (nlocal values)
-  PetscInt dims[3] = {1, 1, 1};  // n_x, n_y, n_z
-  bool has_lam = false;
+  void* stage = nullptr;  // in-place host-Vec staging of the slab path (nl values)
   double lam[6] = {0, 0, 0, 0, 0, 0};
-  uint64_t lam_version = 0;  // the plan's symbol version right after lam was set
-  // the Diag setupFFTPrec3D materialised from the plan's symbol of version diag_version: its
-  // object id and its state right after that write (0 id: none).  The version is the plan's
-  // own counter (cfp_plan_symbol_version), so a symbol set on the plan directly through
-  // MatFFTHIPGetPlan also invalidates the fast path.
-  PetscObjectId diag_id = 0;
-  PetscObjectState diag_state = 0;
-  uint64_t diag_version = 0;
-  PetscInt solves_own = 0, solves_diag = 0;  // solve_3D calls per path (MatFFTHIPGetSolveCounts)
 };
-
-PetscErrorCode fft_shell(Mat A, FFTShell** out) {
-  void* ctx = nullptr;
-  PetscCall(MatShellGetContext(A, &ctx));
-  FFTShell* s = (FFTShell*)ctx;
-  PetscCheck(s && s->magic == kFFTMagic, PETSC_COMM_SELF, PETSC_ERR_ARG_WRONG,
-             "FFT_MAT is not an FFT matrix made by MatCreateFFT/MatCreateFFTHIP");
-  *out = s;
-  return PETSC_SUCCESS;
-}
-
 
 // MatMult / MatMultTranspose: the unnormalised 3-D DFT; several ranks: of the slab-distributed
 // grid, natural slab in and out (FFTW-MPI's non-transposed layout)
 PetscErrorCode fft_mult_impl(Mat A, Vec x, Vec y, bool backward) {
   FFTShell* s;
-  PetscCall(fft_shell(A, &s));
-  const PetscInt n = s->nlocal;
+  PetscCall(shell_of(A, &s));
+  const PetscInt n = s->nl;
   PetscCall(check_size(x, n, "MatMult: x has the wrong size"));
   PetscCall(check_size(y, n, "MatMult: y has the wrong size"));
-  PetscCheck(x != y || !s->dplan, PETSC_COMM_SELF, PETSC_ERR_ARG_IDN, "MatMult: x and y must differ");
+  PetscCheck(x != y || !s->slab.plan, PETSC_COMM_SELF, PETSC_ERR_ARG_IDN, "MatMult: x and y must differ");
   DevIn in;
   DevOut out;
   PetscCall(in.get(x, n));
   PetscCall(out.get(y, n));
   // on the Vec stream, behind the Vec kernels that produced x (a non-blocking stream does not
   // order against the null stream), then waited for: the transforms return complete
-  void* vst = nullptr;
-  bool vwait = true;
-  cfp_pc::device_stream(&vst, &vwait);
+  Stream q;
   int rc;
-  if (s->dplan)
-    rc = backward ? cfp_dist_plan_backward(s->dplan, in.ptr(), out.ptr(), vst)
-                  : cfp_dist_plan_forward(s->dplan, in.ptr(), out.ptr(), vst);
+  if (s->slab.plan)
+    rc = backward ? cfp_dist_plan_backward(s->slab.plan, in.ptr(), out.ptr(), q.st)
+                  : cfp_dist_plan_forward(s->slab.plan, in.ptr(), out.ptr(), q.st);
   else
-    rc = backward ? cfp_plan_backward(s->plan, in.ptr(), out.ptr(), vst)
-                  : cfp_plan_forward(s->plan, in.ptr(), out.ptr(), vst);
-  if (rc == CFP_SUCCESS) rc = cfp_stream_sync(vst);
+    rc = backward ? cfp_plan_backward(s->plan, in.ptr(), out.ptr(), q.st)
+                  : cfp_plan_forward(s->plan, in.ptr(), out.ptr(), q.st);
+  if (rc == CFP_SUCCESS) rc = cfp_stream_sync(q.st);
   PetscCall(out.put());
   PetscCall(in.put());
   CFPCALL(rc);
   return PETSC_SUCCESS;
 }
-#ifdef CFP_WITH_PETSC
-// MatCreateVecsFFTW(A, x, y, z) on the shell: PETSc dispatches it through this composed method
-// (a MATSHELL has no MatCreateVecsFFTW_C of its own)
-PetscErrorCode fft_create_vecs(Mat A, Vec* x, Vec* y, Vec* z) {
-  if (x) PetscCall(MatCreateVecs(A, x, NULL));
-  if (y) PetscCall(MatCreateVecs(A, NULL, y));
-  if (z) PetscCall(MatCreateVecs(A, z, NULL));
-  return PETSC_SUCCESS;
-}
-#endif
 PetscErrorCode fft_mult(Mat A, Vec x, Vec y) { return fft_mult_impl(A, x, y, false); }
 PetscErrorCode fft_mult_transpose(Mat A, Vec x, Vec y) { return fft_mult_impl(A, x, y, true); }
 PetscErrorCode fft_destroy(Mat A) {
   FFTShell* s;
-  PetscCall(fft_shell(A, &s));
+  PetscCall(shell_of(A, &s));
   if (s->plan) cfp_plan_destroy(s->plan);
   slab_destroy(&s->slab);
-  s->dplan = nullptr;
   if (s->stage) hipFree(s->stage);
   s->magic = 0;
   delete s;
@@ -143,166 +94,42 @@ void lam6(PetscScalar lx, PetscScalar ly, PetscScalar lz, double out[6]) {
 
 // Use (or refresh) the plan's separable transport symbol for these lambdas (App. A item 9:
 // the reference rebuilds Diag on every direct-solve call; equal lambdas reuse it here).
-PetscErrorCode symbol_version(FFTShell* s, uint64_t* v) {
-  if (s->dplan) *v = s->dist_version;
-  else CFPCALL(cfp_plan_symbol_version(s->plan, v));
-  return PETSC_SUCCESS;
-}
-
 PetscErrorCode ensure_transport_symbol(FFTShell* s, const double lam[6]) {
-  uint64_t v;
-  PetscCall(symbol_version(s, &v));
-  if (s->has_lam && v == s->lam_version && std::memcmp(s->lam, lam, sizeof(s->lam)) == 0) return PETSC_SUCCESS;
-  if (s->dplan) {
-    CFPCALL(cfp_dist_plan_set_symbol_transport(s->dplan, lam));
+  if (s->has_lam && s->symbol_version() == s->lam_version && std::memcmp(s->lam, lam, sizeof(s->lam)) == 0)
+    return PETSC_SUCCESS;
+  if (s->slab.plan) {
+    CFPCALL(cfp_dist_plan_set_symbol_transport(s->slab.plan, lam));
     ++s->dist_version;
   } else {
     CFPCALL(cfp_plan_set_symbol_transport(s->plan, lam));
   }
   std::memcpy(s->lam, lam, sizeof(s->lam));
   s->has_lam = true;
-  PetscCall(symbol_version(s, &s->lam_version));
+  s->lam_version = s->symbol_version();
   return PETSC_SUCCESS;
-}
-
-// Diag holds exactly the plan's current symbol (materialised by setupFFTPrec3D, untouched since)
-PetscErrorCode diag_is_own_symbol(FFTShell* s, Vec Diag, bool* own) {
-  *own = false;
-  uint64_t v;
-  PetscCall(symbol_version(s, &v));
-  if (!s->diag_id || s->diag_version != v) return PETSC_SUCCESS;
-  PetscObjectId id;
-  PetscObjectState st;
-  PetscCall(PetscObjectGetId((PetscObject)Diag, &id));
-  PetscCall(PetscObjectStateGet((PetscObject)Diag, &st));
-  *own = id == s->diag_id && st == s->diag_state;
-  return PETSC_SUCCESS;
-}
-
-// Per-context additions of this build, keyed by the context's address, so that the context
-// keeps the reference's exact layout (src/PCSHELLFft_3D.hxx:8-21; include/pcshell_fft3d.h).
-struct CtxExtra {
-  Mat remapBack = nullptr;
-};
-std::mutex g_extra_mu;
-std::unordered_map<const void*, CtxExtra> g_extra;
-
-Mat ctx_remap_back(const FFTPrecTransportContext* ctx) {
-  std::lock_guard<std::mutex> g(g_extra_mu);
-  auto it = g_extra.find(ctx);
-  return it == g_extra.end() ? nullptr : it->second.remapBack;
-}
-void ctx_forget(const FFTPrecTransportContext* ctx) {
-  std::lock_guard<std::mutex> g(g_extra_mu);
-  g_extra.erase(ctx);
 }
 
 }  // namespace
 
-extern "C" PetscErrorCode FFTPrecTransportContextSetRemapBack(FFTPrecTransportContext* ctx, Mat remapBack) {
-  PetscCheck(ctx, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "NULL context");
-  std::lock_guard<std::mutex> g(g_extra_mu);
-  if (remapBack) g_extra[ctx].remapBack = remapBack;
-  else g_extra.erase(ctx);
-  return PETSC_SUCCESS;
-}
-extern "C" PetscErrorCode FFTPrecTransportContextGetRemapBack(const FFTPrecTransportContext* ctx, Mat* remapBack) {
-  PetscCheck(ctx && remapBack, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "NULL argument");
-  *remapBack = ctx_remap_back(ctx);
-  return PETSC_SUCCESS;
-}
-
-// the z-slab plan of this rank, its exchanges over `comm` (pcshell_common.h)
-PetscErrorCode create_dist(FFTShell* s, MPI_Comm comm, int dev) {
-  int64_t lay[8];
-  CFPCALL(cfp_slab_layout(s->dims[0], s->dims[1], s->dims[2], s->nranks, s->rank, lay));
-  s->nlocal = lay[4];
-  PetscErrorCode e = slab_create(comm, s->nranks, s->rank, s->dims, dev, &s->slab);
-  s->dplan = s->slab.plan;
-  s->comm = s->slab.comm;
-  return e;
-}
+const int cfp_pc::kShellMagic = 0x46465448;  // "FFTH"
+// a device-Vec PCApply without remaps is the plan apply alone
+const bool cfp_pc::kPlanApplyIsWholePCApply = true;
 
 // ------------------------------------------------------------------ FFT matrix
-// MatCreateFFT(comm, ndim, dims, MATFFTW) of the reference (src/PCSHELLFft_3D.cxx:34-35): one
-// rank -> the single-GPU plan; several -> this rank's z slab (needs nranks | n_z; n_y is split
-// in FFTW-MPI's blocks of ceil(n_y / nranks) rows, any n_y)
+// MatCreateFFT(comm, ndim, dims, MATFFTW) of the reference (src/PCSHELLFft_3D.cxx:34-35): every
+// Vec holds this rank's z-planes of the grid (pcshell_common.h, shell_create_plan)
 extern "C" PetscErrorCode MatCreateFFTHIP(MPI_Comm comm, PetscInt ndim, const PetscInt dims[], Mat* A) {
-  PetscCheck(ndim >= 1 && ndim <= 3, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, "ndim must be 1, 2 or 3");
-  PetscCheck(dims && A, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "NULL argument");
-  int nranks = 1, rank = 0;
-  PetscCallMPI(MPI_Comm_size(comm, &nranks));
-  PetscCallMPI(MPI_Comm_rank(comm, &rank));
   FFTShell* s = new FFTShell;
-  s->comm = comm;
-  s->nranks = nranks;
-  s->rank = rank;
-  // dims are row-major {n_z, n_y, n_x} (src/PCSHELLFft_3D.cxx:34): last = fastest = x
-  for (PetscInt d = 0; d < ndim; ++d) s->dims[d] = dims[ndim - 1 - d];
-  const PetscInt N = s->dims[0] * s->dims[1] * s->dims[2];
-  s->nlocal = N;
-  int dev = 0;
-  hipGetDevice(&dev);
-  if (nranks > 1) {
-    PetscErrorCode e = create_dist(s, comm, dev);
-    if (e) {
-      slab_destroy(&s->slab);
-      delete s;
-      return e;
-    }
-  } else {
-    int rc = cfp_plan_create(&s->plan, s->dims[0], s->dims[1], s->dims[2], dev);
-    if (rc) {
-      delete s;
-      return cfp_err(rc, "MatCreateFFTHIP");
-    }
+  PetscErrorCode e = shell_create_plan(s, comm, ndim, dims, A);
+  if (e) {
+    delete s;
+    return e;
   }
-  PetscCall(MatCreateShell(comm, s->nlocal, s->nlocal, N, N, s, A));
-  PetscCall(MatShellSetOperation(*A, MATOP_MULT, (void (*)(void))fft_mult));
-  PetscCall(MatShellSetOperation(*A, MATOP_MULT_TRANSPOSE, (void (*)(void))fft_mult_transpose));
-  PetscCall(MatShellSetOperation(*A, MATOP_DESTROY, (void (*)(void))fft_destroy));
-#ifdef CFP_WITH_PETSC
-  PetscCall(PetscObjectComposeFunction((PetscObject)*A, "MatCreateVecsFFTW_C", fft_create_vecs));
-#endif
-  return PETSC_SUCCESS;
-}
-
-extern "C" PetscErrorCode MatFFTHIPGetPlan(Mat A, cfp_plan_t* plan) {
-  FFTShell* s;
-  PetscCall(fft_shell(A, &s));
-  *plan = s->plan;
-  return PETSC_SUCCESS;
-}
-
-extern "C" PetscErrorCode MatFFTHIPGetDistPlan(Mat A, cfp_dist_plan_t* plan) {
-  FFTShell* s;
-  PetscCall(fft_shell(A, &s));
-  *plan = s->dplan;
-  return PETSC_SUCCESS;
-}
-
-extern "C" PetscErrorCode MatFFTHIPGetSolveCounts(Mat A, PetscInt* own_symbol, PetscInt* explicit_diag) {
-  FFTShell* s;
-  PetscCall(fft_shell(A, &s));
-  if (own_symbol) *own_symbol = s->solves_own;
-  if (explicit_diag) *explicit_diag = s->solves_diag;
-  return PETSC_SUCCESS;
+  const PetscInt N = s->dims[0] * s->dims[1] * s->dims[2];
+  return shell_create_mat(s, comm, s->nl, s->nl, N, N, fft_mult, fft_mult_transpose, fft_destroy, A);
 }
 
 // ------------------------------------------------------------------ direct solver
-// build_transport_col, src/FftLinearSolver_3D.c:80-90
-extern "C" PetscErrorCode build_transport_col(Vec c, PetscInt size) {
-  PetscFunctionBeginUser;
-  PetscCall(VecSet(c, 0.0));
-  if (size > 1) {
-    PetscCall(VecSetValue(c, 0, 1.0, INSERT_VALUES));
-    PetscCall(VecSetValue(c, 1, -1.0, INSERT_VALUES));
-  }
-  PetscCall(VecAssemblyBegin(c));
-  PetscCall(VecAssemblyEnd(c));
-  PetscFunctionReturn(PETSC_SUCCESS);
-}
-
 // Diag[k] = 1 + lx cx[kx] + ly cy[ky] + lz cz[kz] on this rank's planes [z0, z0 + nzl) (one
 // device sweep; cx, cy, cz device arrays of the full axes)
 PetscErrorCode build_diag_rows(double* diag, const double* cx, const double* cy, const double* cz, PetscInt nx,
@@ -354,24 +181,22 @@ extern "C" PetscErrorCode build_diag_mat_vec_3D(Vec Diag, Vec cx, Vec cy, Vec cz
 // ex (single rank, register symbol, b != X): the fused Krylov step (cfp_plan_apply_ex); ex->fused
 // stays -1 when this apply could not take it.
 PetscErrorCode shell_apply(FFTShell* s, Vec X, Vec b, bool own, Vec Diag, cfp_apply_ex_t* ex = nullptr) {
-  const PetscInt n = s->nlocal;
+  const PetscInt n = s->nl;
   DevIn din;
-  if (!own && !s->dplan) PetscCall(din.get(Diag, n));
-  if (s->dplan) CFPCALL(cfp_dist_plan_use_diag(s->dplan, own ? 0 : 1));
+  if (!own && !s->slab.plan) PetscCall(din.get(Diag, n));
+  if (s->slab.plan) CFPCALL(cfp_dist_plan_use_diag(s->slab.plan, own ? 0 : 1));
   // device Vecs: on the Vec stream, behind the Vec kernels that produced b (the slab apply too,
   // which then waits: its exchanges are host-driven)
-  void* vst = nullptr;
-  bool vwait = true;
-  cfp_pc::device_stream(&vst, &vwait);
+  Stream q;
   if (ex) ex->fused = -1;
   auto dev_apply = [&](const double* in, double* out) -> int {
-    if (s->dplan) return cfp_dist_plan_apply(s->dplan, in, out, vst);
-    if (ex && own && in != out) return cfp_plan_apply_ex(s->plan, in, out, vst, ex);
-    return own ? cfp_plan_apply(s->plan, in, out, vst) : cfp_plan_apply_with_diag(s->plan, din.ptr(), in, out, vst);
+    if (s->slab.plan) return cfp_dist_plan_apply(s->slab.plan, in, out, q.st);
+    if (ex && own && in != out) return cfp_plan_apply_ex(s->plan, in, out, q.st, ex);
+    return own ? cfp_plan_apply(s->plan, in, out, q.st) : cfp_plan_apply_with_diag(s->plan, din.ptr(), in, out, q.st);
   };
   // device Vecs: wait only where the caller cannot rely on stream order
   auto dev_sync = [&]() -> int {
-    if (s->dplan || vwait || din.tmp) return cfp_stream_sync(vst);  // din.tmp: a staged host Diag is freed below
+    if (s->slab.plan || q.wait || din.tmp) return cfp_stream_sync(q.st);  // din.tmp: a staged host Diag is freed below
     return CFP_SUCCESS;
   };
   int rc;
@@ -382,7 +207,7 @@ PetscErrorCode shell_apply(FFTShell* s, Vec X, Vec b, bool own, Vec Diag, cfp_ap
     PetscMemType mt;
     PetscCall(VecGetArrayAndMemType(X, &arr, &mt));
     double* p = (double*)arr;
-    if (mt == PETSC_MEMTYPE_HOST && !s->dplan) {
+    if (mt == PETSC_MEMTYPE_HOST && !s->slab.plan) {
       // staged through the plan's persistent device buffer; both copies are checked, so a
       // failed copy returns PETSC_ERR_LIB instead of leaving stale data behind
       rc = own ? cfp_plan_apply_host(s->plan, p, p) : cfp_plan_apply_with_diag_host(s->plan, din.ptr(), p, p);
@@ -392,7 +217,7 @@ PetscErrorCode shell_apply(FFTShell* s, Vec X, Vec b, bool own, Vec Diag, cfp_ap
       if (!s->stage && hipMalloc(&s->stage, bytes) != hipSuccess) stage_err = PETSC_ERR_MEM;
       if (!stage_err && hipMemcpy(s->stage, p, bytes, hipMemcpyHostToDevice) != hipSuccess) stage_err = PETSC_ERR_LIB;
       if (!stage_err) rc = dev_apply((const double*)s->stage, (double*)s->stage);
-      if (!stage_err && !rc) rc = cfp_stream_sync(vst);
+      if (!stage_err && !rc) rc = cfp_stream_sync(q.st);
       if (!stage_err && !rc && hipMemcpy(p, s->stage, bytes, hipMemcpyDeviceToHost) != hipSuccess)
         stage_err = PETSC_ERR_LIB;
     } else {
@@ -407,11 +232,11 @@ PetscErrorCode shell_apply(FFTShell* s, Vec X, Vec b, bool own, Vec Diag, cfp_ap
     PetscCall(xout.get(X, n));
     rc = dev_apply(bin.ptr(), xout.ptr());
     // a staged host side (DevIn/DevOut copies) needs the result now
-    if (rc == CFP_SUCCESS) rc = (bin.tmp || xout.tmp) ? cfp_stream_sync(vst) : dev_sync();
+    if (rc == CFP_SUCCESS) rc = (bin.tmp || xout.tmp) ? cfp_stream_sync(q.st) : dev_sync();
     PetscCall(xout.put());
     PetscCall(bin.put());
   }
-  if (!own && !s->dplan) PetscCall(din.put());
+  if (!own && !s->slab.plan) PetscCall(din.put());
   PetscCheck(!stage_err, PETSC_COMM_SELF, stage_err, "solve: host staging of the slab failed");
   CFPCALL(rc);
   return PETSC_SUCCESS;
@@ -423,16 +248,16 @@ PetscErrorCode shell_apply(FFTShell* s, Vec X, Vec b, bool own, Vec Diag, cfp_ap
 PetscErrorCode solve_impl(Mat FFT_MAT, Vec X, Vec Diag, Vec b, PetscInt size, cfp_apply_ex_t* ex) {
   PetscFunctionBeginUser;
   FFTShell* s;
-  PetscCall(fft_shell(FFT_MAT, &s));
+  PetscCall(shell_of(FFT_MAT, &s));
   const PetscInt N = s->dims[0] * s->dims[1] * s->dims[2];
   PetscCheck(size == N, PETSC_COMM_SELF, PETSC_ERR_ARG_SIZ, "solve_3D: size != number of grid cells of FFT_MAT");
-  PetscCall(check_size(X, s->nlocal, "solve_3D: X has the wrong size"));
-  PetscCall(check_size(b, s->nlocal, "solve_3D: b has the wrong size"));
-  PetscCall(check_size(Diag, s->nlocal, "solve_3D: Diag has the wrong size"));
+  PetscCall(check_size(X, s->nl, "solve_3D: X has the wrong size"));
+  PetscCall(check_size(b, s->nl, "solve_3D: b has the wrong size"));
+  PetscCall(check_size(Diag, s->nl, "solve_3D: Diag has the wrong size"));
   // the plan's own symbol, if Diag was materialised from it and nothing has written to it since
   bool own = false;
-  PetscCall(diag_is_own_symbol(s, Diag, &own));
-  if (s->dplan) {
+  PetscCall(s->diag_is_own_symbol(Diag, &own));
+  if (s->slab.plan) {
     // every rank must take the same path (the apply holds collectives): agree on it, and on
     // whether the explicit Diag has to be moved into the z-pencil layout again
     PetscObjectId id;
@@ -440,16 +265,14 @@ PetscErrorCode solve_impl(Mat FFT_MAT, Vec X, Vec Diag, Vec b, PetscInt size, cf
     PetscCall(PetscObjectGetId((PetscObject)Diag, &id));
     PetscCall(PetscObjectStateGet((PetscObject)Diag, &st));
     double f[2] = {own ? 0.0 : 1.0, (id == s->dt_id && st == s->dt_state) ? 0.0 : 1.0};
-    PetscCall(comm_max(s->comm, s->nranks, f, 2));
+    PetscCall(comm_max(s->slab.comm, s->nranks, f, 2));
     own = f[0] == 0.0;
     if (!own && f[1] != 0.0) {
       DevIn din;
-      PetscCall(din.get(Diag, s->nlocal));
-      void* vst = nullptr;
-      bool vwait = true;
-      cfp_pc::device_stream(&vst, &vwait);
-      int rc = cfp_dist_plan_set_diag(s->dplan, din.ptr(), vst);
-      if (rc == CFP_SUCCESS) rc = cfp_stream_sync(vst);
+      PetscCall(din.get(Diag, s->nl));
+      Stream q;
+      int rc = cfp_dist_plan_set_diag(s->slab.plan, din.ptr(), q.st);
+      if (rc == CFP_SUCCESS) rc = cfp_stream_sync(q.st);
       PetscCall(din.put());
       CFPCALL(rc);
       s->dt_id = id;
@@ -478,7 +301,7 @@ cfp_apply_ex_t* take_dots(PC pc, cfp_apply_ex_t* ex, PCMiniApplyDots** req, cons
   FFTPrecTransportContext* ctx = nullptr;
   FFTShell* s = nullptr;
   int fusable = 0;
-  if (PCShellGetContext(pc, &ctx) || !ctx || !ctx->FFT_MAT || fft_shell(ctx->FFT_MAT, &s) || !s->plan ||
+  if (PCShellGetContext(pc, &ctx) || !ctx || !ctx->FFT_MAT || shell_of(ctx->FFT_MAT, &s) || !s->plan ||
       cfp_plan_apply_ex_fusable(s->plan, pre, (int)(*req)->nv, &fusable) || !fusable) {
     *req = nullptr;
     return nullptr;
@@ -497,7 +320,7 @@ extern "C" PetscErrorCode FftTransportSolver(PetscInt nx, PetscInt ny, PetscInt 
                                              PetscScalar lz, Vec X, Vec b, Mat FFT_MAT) {
   PetscFunctionBeginUser;
   FFTShell* s;
-  PetscCall(fft_shell(FFT_MAT, &s));
+  PetscCall(shell_of(FFT_MAT, &s));
   PetscCheck(s->dims[0] * s->dims[1] * s->dims[2] == nx * ny * nz, PETSC_COMM_SELF, PETSC_ERR_ARG_SIZ,
              "FftTransportSolver: n_x n_y n_z does not match FFT_MAT");
   PetscCheck(s->dims[0] == nx && s->dims[1] == ny && s->dims[2] == nz, PETSC_COMM_SELF, PETSC_ERR_ARG_SIZ,
@@ -505,146 +328,73 @@ extern "C" PetscErrorCode FftTransportSolver(PetscInt nx, PetscInt ny, PetscInt 
   double lam[6];
   lam6(lx, ly, lz, lam);
   PetscCall(ensure_transport_symbol(s, lam));
-  PetscCall(check_size(X, s->nlocal, "FftTransportSolver: X has the wrong size"));
-  PetscCall(check_size(b, s->nlocal, "FftTransportSolver: b has the wrong size"));
+  PetscCall(check_size(X, s->nl, "FftTransportSolver: X has the wrong size"));
+  PetscCall(check_size(b, s->nl, "FftTransportSolver: b has the wrong size"));
   PetscCall(shell_apply(s, X, b, true, nullptr));
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 
-// Fft3DTransportSolver, :266-281: lambda_d = a_d dt / delta_d
-extern "C" PetscErrorCode Fft3DTransportSolver(PetscInt nx, PetscInt ny, PetscInt nz, PetscScalar ax, PetscScalar ay,
-                                               PetscScalar az, PetscScalar dt, PetscScalar dx, PetscScalar dy,
-                                               PetscScalar dz, Vec X, Vec b, Mat FFT_MAT) {
-  PetscFunctionBeginUser;
-  const PetscScalar lx = ax * dt / dx, ly = ay * dt / dy, lz = az * dt / dz;
-  PetscCall(FftTransportSolver(nx, ny, nz, lx, ly, lz, X, b, FFT_MAT));
-  PetscFunctionReturn(PETSC_SUCCESS);
-}
-// :283-290
-extern "C" PetscErrorCode Fft2DTransportSolver(PetscInt nx, PetscInt ny, PetscScalar ax, PetscScalar ay,
-                                               PetscScalar dt, PetscScalar dx, PetscScalar dy, Vec X, Vec b,
-                                               Mat FFT_MAT) {
-  PetscFunctionBeginUser;
-  PetscCall(Fft3DTransportSolver(nx, ny, 1, ax, ay, 0.0, dt, dx, dy, 1.0, X, b, FFT_MAT));
-  PetscFunctionReturn(PETSC_SUCCESS);
-}
-// :292-301
-extern "C" PetscErrorCode Fft1DTransportSolver(PetscInt nx, PetscScalar ax, PetscScalar dt, PetscScalar dx, Vec X,
-                                               Vec b, Mat FFT_MAT) {
-  PetscFunctionBeginUser;
-  PetscCall(Fft3DTransportSolver(nx, 1, 1, ax, 0.0, 0.0, dt, dx, 1.0, 1.0, X, b, FFT_MAT));
-  PetscFunctionReturn(PETSC_SUCCESS);
-}
-// :303-312 (context by value, as the reference)
-extern "C" PetscErrorCode PetscFft3DTransportSolver(struct StructuredTransportContext c, Vec b, Vec x) {
-  PetscFunctionBeginUser;
-  PetscCall(Fft3DTransportSolver(c.n_x, c.n_y, c.n_z, c.a_x, c.a_y, c.a_z, c.dt, c.delta_x, c.delta_y, c.delta_z, x,
-                                 b, c.FFT_MAT));
-  PetscFunctionReturn(PETSC_SUCCESS);
-}
-
 // ------------------------------------------------------------------ PCSHELL callbacks
-// applyFFT3DPrecTransport, src/PCSHELLFft_3D.cxx:10-24
-extern "C" PetscErrorCode applyFFT3DPrecTransport(PC pc, Vec b, Vec x) {
-  PetscFunctionBeginUser;
-  FFTPrecTransportContext* ctx = nullptr;
-  PetscCall(PCShellGetContext(pc, &ctx));
-  PetscCheck(ctx && ctx->FFT_MAT && ctx->Diag, PETSC_COMM_SELF, PETSC_ERR_ARG_WRONGSTATE,
-             "applyFFT3DPrecTransport: setupFFTPrec3D has not run");
+// the solve of applyFFT3DPrecTransport (pcshell_boundary.cpp)
+PetscErrorCode cfp_pc::pc_solve(PC pc, FFTPrecTransportContext* ctx, Vec X, Vec src) {
   const PetscInt N = ctx->n_x * ctx->n_y * ctx->n_z;
-  Vec src = b;
-  // the stand-in KSP times a PCApply by the plan's first and last kernel only when the plan
-  // apply is the whole PCApply: not with remaps around it
-  if (ctx->intersectionMatrix || ctx_remap_back(ctx)) cfp_apply_stamp_clear();
-  if (ctx->intersectionMatrix) {  // mesh -> Cartesian remap (identity when NULL)
-    PetscCall(MatMult(ctx->intersectionMatrix, b, ctx->b_cartesien));
-    src = ctx->b_cartesien;
-  }
-  if (Mat back = ctx_remap_back(ctx)) {  // extra (mesh_unstructured.h): solve on the grid, then back to the mesh
-    if (src != ctx->b_cartesien) PetscCall(VecCopy(src, ctx->b_cartesien));
-    PetscCall(solve_3D(ctx->FFT_MAT, ctx->b_cartesien, ctx->Diag, ctx->b_cartesien, ctx->b_hat, N));
-    PetscCall(MatMult(back, ctx->b_cartesien, x));
-    PetscFunctionReturn(PETSC_SUCCESS);
-  }
+  cfp_apply_ex_t* ex = nullptr;
 #ifndef CFP_WITH_PETSC
   // the stand-in KSP may ask for dots of x with its basis (PCMiniApplyDots): they ride in the apply
   cfp_apply_ex_t exd{};
   PCMiniApplyDots* req = nullptr;
-  cfp_apply_ex_t* ex = take_dots(pc, &exd, &req);
-  PetscCall(solve_impl(ctx->FFT_MAT, x, ctx->Diag, src, N, ex));
-  if (req && exd.fused >= 0) req->done = PETSC_TRUE;
-#else
-  PetscCall(solve_3D(ctx->FFT_MAT, x, ctx->Diag, src, ctx->b_hat, N));
+  if (pc) ex = take_dots(pc, &exd, &req);
 #endif
-  PetscFunctionReturn(PETSC_SUCCESS);
+  PetscCall(solve_impl(ctx->FFT_MAT, X, ctx->Diag, src, N, ex));
+#ifndef CFP_WITH_PETSC
+  if (req && exd.fused >= 0) req->done = PETSC_TRUE;
+#endif
+  return PETSC_SUCCESS;
 }
 
-// PCShellSetApplyBA callback (PETSc's PCApplyBAorAB on a shell): y = B A x (left) or A B x
-// (right) with A the PC's operator.  One rank, left, register symbol, no remaps, and A the
-// stand-in AIJ in row-class form: A x is formed inside the apply's first sweep (cfp_apply_ex_t,
-// P1 reads x once) instead of a MatMult sweep into `work` -- config 3's transport operator couples
-// cells along x only, so the whole stencil of a row is in the rows P1 loads.  Anything else:
-// MatMult, then the apply, as PETSc does without an applyBA.
-extern "C" PetscErrorCode applyFFT3DPrecTransportBA(PC pc, PCSide side, Vec x, Vec y, Vec work) {
-  PetscFunctionBeginUser;
-  FFTPrecTransportContext* ctx = nullptr;
-  PetscCall(PCShellGetContext(pc, &ctx));
-  PetscCheck(ctx && ctx->FFT_MAT && ctx->Diag, PETSC_COMM_SELF, PETSC_ERR_ARG_WRONGSTATE,
-             "applyFFT3DPrecTransportBA: setupFFTPrec3D has not run");
-  Mat A = nullptr;
-  PetscCall(PCGetOperators(pc, &A, NULL));
-  PetscCheck(A, PETSC_COMM_SELF, PETSC_ERR_ARG_WRONGSTATE, "applyFFT3DPrecTransportBA: the PC has no operator");
+// The fused step of applyFFT3DPrecTransportBA (pcshell_boundary.cpp).  One rank, register symbol,
+// and A the stand-in AIJ in row-class form: A x is formed inside the apply's first sweep
+// (cfp_apply_ex_t, P1 reads x once) instead of a MatMult sweep into `work` -- config 3's transport
+// operator couples cells along x only, so the whole stencil of a row is in the rows P1 loads.
+PetscErrorCode cfp_pc::pc_fused_ba(PC pc, FFTPrecTransportContext* ctx, Mat A, Vec x, Vec y, bool* taken) {
+  *taken = false;
 #ifndef CFP_WITH_PETSC
-  if (side == PC_LEFT && !ctx->intersectionMatrix && !ctx_remap_back(ctx) && x != y) {
-    FFTShell* s;
-    PetscCall(fft_shell(ctx->FFT_MAT, &s));
-    bool own = false;
-    PetscCall(diag_is_own_symbol(s, ctx->Diag, &own));
-    PetscInt am, an;
-    PetscCall(MatGetSize(A, &am, &an));
-    const PetscInt N = ctx->n_x * ctx->n_y * ctx->n_z;
-    if (!s->dplan && own && am == N && an == N) {
-      PetscBool has = PETSC_FALSE, xl = PETSC_FALSE;
-      PetscMiniDia dia;
-      PetscCall(PetscMiniMatAIJGetDia(A, ctx->n_x, &has, &xl, &dia));
-      cfp_stencil_t st;
-      int fusable = 0;
-      if (has) {
-        std::memset((void*)&st, 0, sizeof(st));
-        st.cls = dia.cls;
-        st.mask = dia.mask;
-        st.tab = (const double*)dia.tab;
-        for (int k = 0; k < 8; ++k) st.off[k] = dia.off[k];
-        st.nd = dia.nd;
-        st.ncls = dia.ncls;
-        st.x_local = xl ? 1 : 0;
-        st.cls_x = dia.cls_x;
-        CFPCALL(cfp_plan_apply_ex_fusable(s->plan, &st, 0, &fusable));
-      }
-      if (fusable) {  // A x inside the apply's first sweep (else MatMult below: the same kernels)
-        cfp_apply_ex_t ex{};
-        PCMiniApplyDots* req = nullptr;
-        take_dots(pc, &ex, &req, &st);
-        ex.pre = &st;
-        ++s->solves_own;
-        PetscCall(shell_apply(s, y, x, true, nullptr, &ex));
-        PetscCheck(ex.fused >= 0, PETSC_COMM_SELF, PETSC_ERR_PLIB, "applyFFT3DPrecTransportBA: fused apply not taken");
-        if (req) req->done = PETSC_TRUE;
-        PetscFunctionReturn(PETSC_SUCCESS);
-      }
-    }
-  }
+  FFTShell* s;
+  PetscCall(shell_of(ctx->FFT_MAT, &s));
+  bool own = false;
+  PetscCall(s->diag_is_own_symbol(ctx->Diag, &own));
+  PetscInt am, an;
+  PetscCall(MatGetSize(A, &am, &an));
+  const PetscInt N = ctx->n_x * ctx->n_y * ctx->n_z;
+  if (s->slab.plan || !own || am != N || an != N) return PETSC_SUCCESS;
+  PetscBool has = PETSC_FALSE, xl = PETSC_FALSE;
+  PetscMiniDia dia;
+  PetscCall(PetscMiniMatAIJGetDia(A, ctx->n_x, &has, &xl, &dia));
+  if (!has) return PETSC_SUCCESS;
+  cfp_stencil_t st;
+  int fusable = 0;
+  std::memset((void*)&st, 0, sizeof(st));
+  st.cls = dia.cls;
+  st.mask = dia.mask;
+  st.tab = (const double*)dia.tab;
+  for (int k = 0; k < 8; ++k) st.off[k] = dia.off[k];
+  st.nd = dia.nd;
+  st.ncls = dia.ncls;
+  st.x_local = xl ? 1 : 0;
+  st.cls_x = dia.cls_x;
+  CFPCALL(cfp_plan_apply_ex_fusable(s->plan, &st, 0, &fusable));
+  if (!fusable) return PETSC_SUCCESS;  // the caller's MatMult, then the apply: the same kernels
+  cfp_apply_ex_t ex{};
+  PCMiniApplyDots* req = nullptr;
+  take_dots(pc, &ex, &req, &st);
+  ex.pre = &st;
+  ++s->solves_own;
+  PetscCall(shell_apply(s, y, x, true, nullptr, &ex));
+  PetscCheck(ex.fused >= 0, PETSC_COMM_SELF, PETSC_ERR_PLIB, "applyFFT3DPrecTransportBA: fused apply not taken");
+  if (req) req->done = PETSC_TRUE;
+  *taken = true;
 #endif
-  if (side == PC_LEFT) {
-    PetscCall(MatMult(A, x, work));
-    PetscCall(applyFFT3DPrecTransport(pc, work, y));
-  } else if (side == PC_RIGHT) {
-    PetscCall(applyFFT3DPrecTransport(pc, x, work));
-    PetscCall(MatMult(A, work, y));
-  } else {
-    PetscCheck(false, PETSC_COMM_SELF, PETSC_ERR_SUP, "applyFFT3DPrecTransportBA: left or right preconditioning");
-  }
-  PetscFunctionReturn(PETSC_SUCCESS);
+  return PETSC_SUCCESS;
 }
 
 // setupFFTPrec3D, :26-84: FFT matrix, work vectors and Diag (materialised from the closed form
@@ -663,14 +413,14 @@ extern "C" PetscErrorCode setupFFTPrec3D(PC pc) {
   PetscCall(MatCreateVecsFFTW(ctx->FFT_MAT, NULL, &ctx->Diag, NULL));
   PetscCall(MatCreateVecsFFTW(ctx->FFT_MAT, &ctx->b_cartesien, &ctx->b_hat, NULL));
   FFTShell* s;
-  PetscCall(fft_shell(ctx->FFT_MAT, &s));
+  PetscCall(shell_of(ctx->FFT_MAT, &s));
   double lam[6];
   lam6(ctx->lambda_x, ctx->lambda_y, ctx->lambda_z, lam);
   PetscCall(ensure_transport_symbol(s, lam));
   DevOut d;
-  PetscCall(d.get(ctx->Diag, s->nlocal));
+  PetscCall(d.get(ctx->Diag, s->nl));
   PetscErrorCode e = PETSC_SUCCESS;
-  if (s->dplan) {  // this rank's z-planes of the closed-form Diag
+  if (s->slab.plan) {  // this rank's z-planes of the closed-form Diag
     const PetscInt nx = ctx->n_x, ny = ctx->n_y, nz = ctx->n_z;
     std::vector<double> h(2 * (size_t)(nx + ny + nz));
     int rc = cfp_transport_symbol_1d(nx, h.data());
@@ -683,7 +433,7 @@ extern "C" PetscErrorCode setupFFTPrec3D(PC pc) {
     PetscCall(VecGetOwnershipRange(ctx->Diag, &lo, NULL));
     const double* td = (const double*)t;
     if (!rc) e = build_diag_rows(d.ptr(), td, td + 2 * nx, td + 2 * (nx + ny), nx, ny, lo / (nx * ny),
-                                 s->nlocal / (nx * ny), lam);
+                                 s->nl / (nx * ny), lam);
     if (t) hipFree(t);
     if (rc) e = cfp_err(rc, "setupFFTPrec3D");
   } else {
@@ -699,83 +449,13 @@ extern "C" PetscErrorCode setupFFTPrec3D(PC pc) {
   Mat A = nullptr;
   PetscCall(PCGetOperators(pc, &A, NULL));
   MatType mt = nullptr;
-  if (A && !s->dplan) PetscCall(MatGetType(A, &mt));
+  if (A && !s->slab.plan) PetscCall(MatGetType(A, &mt));
   if (mt && std::strcmp(mt, MATSEQAIJ) == 0) {
     PetscBool has, xl;
     PetscMiniDia dia;
     PetscCall(PetscMiniMatAIJGetDia(A, ctx->n_x, &has, &xl, &dia));
   }
 #endif
-  // remember which object and state hold the symbol (solve_3D's register-symbol fast path)
-  PetscCall(PetscObjectGetId((PetscObject)ctx->Diag, &s->diag_id));
-  PetscCall(PetscObjectStateGet((PetscObject)ctx->Diag, &s->diag_state));
-  PetscCall(symbol_version(s, &s->diag_version));
+  PetscCall(s->remember_diag(ctx->Diag));
   PetscFunctionReturn(PETSC_SUCCESS);
-}
-
-// destroyFFTPrec3D, :86-99 (frees what setup created; the context itself stays the caller's)
-extern "C" PetscErrorCode destroyFFTPrec3D(PC pc) {
-  PetscFunctionBeginUser;
-  FFTPrecTransportContext* ctx = nullptr;
-  PetscCall(PCShellGetContext(pc, &ctx));
-  if (!ctx) PetscFunctionReturn(PETSC_SUCCESS);
-  PetscCall(VecDestroy(&ctx->Diag));
-  PetscCall(VecDestroy(&ctx->b_cartesien));
-  PetscCall(VecDestroy(&ctx->b_hat));
-  PetscCall(MatDestroy(&ctx->FFT_MAT));
-  PetscFunctionReturn(PETSC_SUCCESS);
-}
-
-// getFFTPrec3DContext, :101-151 (fills the caller's ctx; lambda formula kept as the reference's)
-extern "C" PetscErrorCode getFFTPrec3DContext(PetscInt ndim, PetscScalar dt, PetscInt nbCells, PetscScalar a_x,
-                                              PetscScalar a_y, PetscScalar a_z, PetscScalar Xmin, PetscScalar Ymin,
-                                              PetscScalar Zmin, PetscScalar Xmax, PetscScalar Ymax, PetscScalar Zmax,
-                                              FFTPrecTransportContext* ctx) {
-  PetscFunctionBeginUser;
-  PetscCheck(ndim > 0 && ndim < 4, PETSC_COMM_WORLD, PETSC_ERR_ARG_OUTOFRANGE, "Dimension should be 1, 2 or 3");
-  PetscCheck(ctx, PETSC_COMM_WORLD, PETSC_ERR_ARG_NULL, "getFFTPrec3DContext: ctx is NULL");
-  PetscInt nx, ny, nz;
-  if (ndim == 3) {
-    nx = (PetscInt)std::floor(std::cbrt((double)nbCells));
-    ny = nx;
-    nz = nx;
-  } else if (ndim == 2) {
-    nx = (PetscInt)std::floor(std::sqrt((double)nbCells));
-    ny = nx;
-    nz = 1;
-  } else {
-    nx = nbCells;
-    ny = 1;
-    nz = 1;
-  }
-  std::memset((void*)ctx, 0, sizeof(*ctx));
-  ctx_forget(ctx);  // a fresh context: no remapBack left from a previous one at this address
-  ctx->spaceDim = ndim;
-  ctx->n_x = nx;
-  ctx->n_y = ny;
-  ctx->n_z = nz;
-  ctx->lambda_x = a_x * dt * (Xmax - Xmin) / (double)nx;
-  ctx->lambda_y = a_y * dt * (Ymax - Ymin) / (double)ny;
-  ctx->lambda_z = a_z * dt * (Zmax - Zmin) / (double)nz;
-  PetscFunctionReturn(PETSC_SUCCESS);
-}
-
-extern "C" FFTPrecTransportContext* FFTPrecTransportContextLast(void) {
-  static FFTPrecTransportContext last{};
-  return &last;
-}
-
-extern "C" PetscErrorCode FFTPrecTransportContextCreate(FFTPrecTransportContext** ctx) {
-  PetscCheck(ctx, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "NULL output");
-  *ctx = new FFTPrecTransportContext;
-  std::memset((void*)*ctx, 0, sizeof(**ctx));
-  return PETSC_SUCCESS;
-}
-extern "C" PetscErrorCode FFTPrecTransportContextDestroy(FFTPrecTransportContext** ctx) {
-  if (ctx && *ctx) {
-    ctx_forget(*ctx);
-    delete *ctx;
-    *ctx = nullptr;
-  }
-  return PETSC_SUCCESS;
 }

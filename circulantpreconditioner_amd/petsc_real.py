@@ -91,6 +91,7 @@ def _declare(L) -> None:
         "PCShellSetApply": ([vp, vp], c_int),
         "PCShellSetDestroy": ([vp, vp], c_int),
         "PCSetUp": ([vp], c_int),
+        "PCSetOperators": ([vp, vp, vp], c_int),
         "PCApply": ([vp, vp, vp], c_int),
         "PCDestroy": ([P(vp)], c_int),
         "KSPCreate": ([c_int, P(vp)], c_int),
@@ -109,6 +110,7 @@ def _declare(L) -> None:
         "setupFFTPrec3D": ([vp], c_int),
         "destroyFFTPrec3D": ([vp], c_int),
         "applyFFT3DPrecTransport": ([vp, vp, vp], c_int),
+        "applyFFT3DPrecTransportBA": ([vp, c_int, vp, vp, vp], c_int),
         "getFFTPrec3DContext": ([i64, d, i64, d, d, d, d, d, d, d, d, d, P(FFTPrecTransportContext)], c_int),
     }
     for name, (args, res) in sig.items():

@@ -92,6 +92,70 @@ def test_real_pcshell(R, oracle, dims, hip):
     R.PetscCall(R.lib().PCDestroy(ctypes.byref(pcp)))
 
 
+@pytest.mark.parametrize("dims", [(8, 4, 2), (9, 4, 6)])
+@pytest.mark.parametrize("hip", [True, False])
+def test_real_intersection_matrix_remap(R, oracle, dims, hip):
+    """A permutation intersectionMatrix (mesh numbering -> Cartesian) is applied before the real
+    solve: PCApply gives the oracle's solve of the permuted b.  (9, 4, 6): odd n_x, a half
+    spectrum of 5 columns, the complex plan on the promoted b."""
+    import scipy.sparse as sp
+    nx, ny, nz = dims
+    N = nx * ny * nz
+    lam = (0.6, 0.15, 0.02)
+    perm = np.random.default_rng(0).permutation(N)
+    A = R.mat_aij(sp.csr_matrix((np.ones(N), perm, np.arange(N + 1)), shape=(N, N)))  # (A b)[i] = b[perm[i]]
+    ctx = R.FFTPrecTransportContext(3, nx, ny, nz, lam[0], lam[1], lam[2], None, A.value, None, None, None)
+    pc = R.pc_shell(ctx)
+    b = oracle.c_fill_uniform(N, 4).real.copy()
+    vb, vx = R.Vec.seq(N, hip=hip).set_array(b), R.Vec.seq(N, hip=hip)
+    R.PetscCall(R.lib().PCApply(pc, vb.h, vx.h))
+    ref = _oracle_solve(oracle, dims, lam, b[perm])
+    assert np.linalg.norm(vx.array() - ref) / np.linalg.norm(ref) < TOL
+    vb.destroy()
+    vx.destroy()
+    pcp = ctypes.c_void_p(pc.value)
+    R.PetscCall(R.lib().PCDestroy(ctypes.byref(pcp)))
+    R.PetscCall(R.lib().MatDestroy(ctypes.byref(A)))
+
+
+@pytest.mark.parametrize("hip", [True, False])
+def test_real_apply_ba_is_matmult_then_pcapply(R, oracle, hip):
+    """applyFFT3DPrecTransportBA on real scalars (no fused form): left y = B (A x), right
+    y = A (B x) -- exactly MatMult with the PC's operator and PCApply, the same kernels."""
+    from oracle import transport as OT
+    L = R.lib()
+    dims, lam = (8, 4, 2), (0.6, 0.15, 0.02)
+    N = 64
+    h = tuple(1.0 / n for n in dims)
+    Acsr = OT.divergence_matrix(dims, h, 0.05, (1.0, 0.5, 0.25), sign="fixed", shift=1.0).real.tocsr()
+    Acsr.sort_indices()
+    A = R.mat_aij(Acsr)
+    ctx = R.FFTPrecTransportContext(3, dims[0], dims[1], dims[2], lam[0], lam[1], lam[2], None, None, None, None, None)
+    pc = R.pc_shell(ctx)
+    R.PetscCall(L.PCSetOperators(pc, A, A))
+    x = oracle.c_fill_uniform(N, 47).real.copy()
+    vx, vy, vw, vy2 = (R.Vec.seq(N, hip=hip) for _ in range(4))
+    vx.set_array(x)
+    PC_LEFT, PC_RIGHT = 0, 1
+    R.PetscCall(L.applyFFT3DPrecTransportBA(pc, PC_LEFT, vx.h, vy.h, vw.h))
+    R.PetscCall(L.MatMult(A, vx.h, vw.h))
+    R.PetscCall(L.PCApply(pc, vw.h, vy2.h))
+    left = vy.array()
+    assert np.array_equal(left, vy2.array())
+    assert np.linalg.norm(left - _oracle_solve(oracle, dims, lam, Acsr @ x)) < TOL * np.linalg.norm(left)
+    R.PetscCall(L.applyFFT3DPrecTransportBA(pc, PC_RIGHT, vx.h, vy.h, vw.h))
+    R.PetscCall(L.PCApply(pc, vx.h, vw.h))
+    R.PetscCall(L.MatMult(A, vw.h, vy2.h))
+    right = vy.array()
+    assert np.array_equal(right, vy2.array())
+    assert not np.array_equal(left, right)  # the two sides really differ
+    for v in (vx, vy, vw, vy2):
+        v.destroy()
+    pcp = ctypes.c_void_p(pc.value)
+    R.PetscCall(L.PCDestroy(ctypes.byref(pcp)))
+    R.PetscCall(L.MatDestroy(ctypes.byref(A)))
+
+
 @pytest.mark.parametrize("dims", [(32, 16, 24), (9, 4, 6), (10, 10, 10), (16, 1, 1)])
 def test_real_matmult_is_fftw_r2c(R, dims):
     """MatMult = r2c (FFTW_FORWARD, unnormalised) into the half spectrum; MatMultTranspose = c2r
