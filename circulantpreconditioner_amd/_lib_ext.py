@@ -99,6 +99,7 @@ def declare(L) -> None:
     i64, dp, vp, c_int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int
     S, P, cs = PetscScalar, ctypes.POINTER, ctypes.c_char_p
     sig = {
+        "cfp_plan_mid_kernel": ([vp, P(c_int)], c_int), "cfp_transport_z_ratio": ([i64, i64, dp, P(ctypes.c_double)], c_int),
         # slab-distributed plan over RCCL + single-process group
         "cfp_dist_get_unique_id": ([ctypes.c_char_p], c_int),
         "cfp_dist_unique_id_bytes": ([], c_int),

@@ -94,6 +94,24 @@ std::vector<cd> host_transport_symbol(i64 n) {
   return s;
 }
 
+// max over (kx, ky) of |lamz / (1 + sx[kx] + sy[ky] + lamz)|, s_d = lambda_d (1 - e^{-2 pi i k / n_d}):
+// the ratio a of the z recurrence u_z = a u_{z-1} + w_z that the transport symbol's z part is
+// (cfp_three_pass.hip k_tp_mid_rec).  A zero denominator gives infinity.
+double transport_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz) {
+  double amax = 0.0;
+  const double lzn = std::abs(lz);
+  for (const cd& y : sy)
+    for (const cd& x : sx) {
+      const std::complex<double> den(x.x + y.x + 1.0 + lz.real(), x.y + y.y + lz.imag());
+      const double d = std::abs(den);
+      const double r = d > 0.0 ? lzn / d : (lzn > 0.0 ? INFINITY : 0.0);
+      if (!(r <= amax)) amax = r;
+    }
+  return amax;
+}
+// the recurrence's rounding grows like eps / (1 - |a|): this cap keeps it near 1e-12
+constexpr double kZrecMaxRatio = 1.0 - 1.0 / 8192.0;
+
 int ilog2_exact(i64 v) {
   if (v <= 0 || (v & (v - 1))) return -1;
   int l = 0;
@@ -161,6 +179,12 @@ struct cfp_plan_s {
   i64 chunk_planes = 0;      // > 0: chunked x/y schedule (see apply_steps)
   int schedule = CFP_SCHEDULE_AUTO;
   TPShape tp_shape;          // 3-sweep kernel shape (cfp_plan_set_three_pass_shape)
+  // the transport symbol's z ratio (cfp_plan_set_symbol_transport): zrec_ok = every column's
+  // |lamz / (1 + s_x + s_y + lamz)| <= 1 - 2^-13, so the 256^3 P2 may solve z by recurrence
+  // (k_tp_mid_rec).  Any other symbol setter clears it.
+  bool zrec_ok = false;
+  double zrec_amax = 0.0;
+  cd lamz = cfp::make_cd(0.0, 0.0);
   bool external_x = false;  // x transformed by the caller (real plan): y/z passes only, no 1/N
   // long axes (n > 4096): four-step split n = n1 n2, both <= 4096 (0: a short axis).  Their
   // spectrum stays in position order p = m1 + n1 m2 for frequency m = m2 + n2 m1.
@@ -228,6 +252,11 @@ bool use_three_pass(const cfp_plan_s* p, bool diag_override) {
                      (p->n[0] == 256 || p->n[0] == 128 || p->n[0] == 100 || p->n[0] == 512));
   if (!want || diag_override || p->sym_kind != 1 || p->external_x) return false;
   return three_pass_supported(p->n) || three_pass_sq_supported(p->n);
+}
+// the plan's next apply runs the recurrence P2
+bool plan_zrec(const cfp_plan_s* p) {
+  return p->zrec_ok && p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
+         three_pass_zrec_shape((int)p->n[0], p->tp_shape);
 }
 
 // the plane schedule (n_x = n_y in {32, 64, 100, 128}, n_z > 1): plane forward (x + y DFTs of
@@ -465,6 +494,10 @@ int run_apply(cfp_plan_s* p, const cd* diag_override, const cd* b, cd* x, hipStr
         e = launch_three_pass_fused(2, tn, tin, tout, a, s, p3grid);
       } else {
         a.krylov = fz != nullptr || g_apply_stamp.start != nullptr;  // an apply inside the stand-in KSP
+        if (q.tp == 1 && plan_zrec(p)) {
+          a.zrec = 1;
+          a.lamz = p->lamz;
+        }
         e = launch_three_pass(q.tp, tn, tin, tout, a, p->tp_shape, s);
       }
       g_stamp = LaunchStamp{};
@@ -622,8 +655,10 @@ int set_separable(cfp_plan_s* p, const std::vector<cd> hat[3], const double lam[
     }
   }
   ++p->sym_version;
+  p->zrec_ok = false;
   return upload_separable(p, s);
 }
+
 
 }  // namespace
 
@@ -723,7 +758,34 @@ extern "C" int cfp_plan_set_symbol_transport(cfp_plan_t p, const double lam[6]) 
   DeviceGuard dg(p->device);
   std::vector<cd> hat[3];
   for (int a = 0; a < 3; ++a) hat[a] = host_transport_symbol(p->n[a]);
-  return set_separable(p, hat, lam);
+  int rc = set_separable(p, hat, lam);
+  if (rc) return rc;
+  if (p->n[0] == 256 && p->n[1] == 256 && p->n[2] == 256) {  // the one grid k_tp_mid_rec is built for
+    const std::complex<double> lz = lamc(lam, 2);
+    p->zrec_amax = transport_z_ratio(p->sym1d[0], p->sym1d[1], lz);
+    p->zrec_ok = p->zrec_amax <= kZrecMaxRatio;
+    p->lamz = make_cd(lz.real(), lz.imag());
+  }
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_plan_mid_kernel(cfp_plan_t p, int* kind) {
+  if (!p || !kind) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  *kind = plan_zrec(p) ? 1 : 0;
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_transport_z_ratio(int64_t nx, int64_t ny, const double lam[6], double* amax) {
+  if (!lam || !amax) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  if (nx < 1 || ny < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
+  std::vector<cd> s[2] = {host_transport_symbol(nx), host_transport_symbol(ny)};
+  for (int a = 0; a < 2; ++a)
+    for (cd& v : s[a]) {
+      const std::complex<double> t = std::complex<double>(v.x, v.y) * lamc(lam, a);
+      v = make_cd(t.real(), t.imag());
+    }
+  *amax = transport_z_ratio(s[0], s[1], lamc(lam, 2));
+  return CFP_SUCCESS;
 }
 
 extern "C" int cfp_plan_set_symbol_separable(cfp_plan_t p, const double* cx, const double* cy, const double* cz,
@@ -745,6 +807,7 @@ extern "C" int cfp_plan_set_diag(cfp_plan_t p, const double* diag, int on_device
   DeviceGuard dg(p->device);
   free_symbol(p);
   ++p->sym_version;
+  p->zrec_ok = false;
   HIPCHK(hipMalloc(&p->diag, sizeof(cd) * (size_t)p->N));
   HIPCHK(hipMemcpy(p->diag, diag, sizeof(cd) * (size_t)p->N, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   p->sym_kind = 2;

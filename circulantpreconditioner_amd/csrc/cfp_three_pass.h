@@ -43,6 +43,11 @@ struct TPArgs {
   // kernel trace lists the in-solver P2 apart from the bare apply's (the two run at different
   // clocks); no effect on the work.
   int krylov = 0;
+  // 1: the symbol is the transport symbol with |lamz / (1 + s_x + s_y + lamz)| <= 1 - 2^-13 on
+  // every column (cfp_plan_set_symbol_transport decides): the default 256^3 P2 solves z by the
+  // recurrence u_z = a u_{z-1} + w_z (k_tp_mid_rec) instead of transforming it.  lamz = lambda_z.
+  int zrec = 0;
+  cd lamz = make_cd(0.0, 0.0);
 };
 
 
@@ -59,7 +64,7 @@ enum { TP_MID_DEFAULT = 0, TP_MID_LANE64 = 1, TP_MID_LANE32 = 2, TP_MID_SWAP64 =
        TP_MID_BLOCKED = 5, TP_MID_BLOCKED32 = 6, TP_MID_SWAP32X = 7, TP_MID_ROWSALT = 8 };
 struct TPShape {
   int n1 = 0;   // y split ny = n1 * n2: 0 (default 32), 32 or 64
-  int mid = 0;  // TP_MID_* (DEFAULT = SWAP64_PF at 256^3)
+  int mid = 0;  // TP_MID_* (DEFAULT = SWAP64_PF at 256^3, or k_tp_mid_rec with TPArgs::zrec)
 };
 
 // the fused stencil's limits (LDS table in P1)
@@ -69,6 +74,10 @@ struct TPShape {
 bool three_pass_fused_supported(int n, TPShape shape);
 hipError_t launch_three_pass_fused(int stage, int n, const cd* in, cd* out, const TPArgs& a, hipStream_t s,
                                    unsigned* grid_out);
+
+// the shapes whose P2 has the recurrence kernel (k_tp_mid_rec, TPArgs::zrec): 256^3, mid =
+// DEFAULT, y split 32 x 8.  SWAP64_PF is the same shape with the FFT kernel, always.
+bool three_pass_zrec_shape(int n, TPShape shape);
 
 bool three_pass_supported(const i64 n[3]);
 // 100^3 (n = R^2, R = 10: cfp_three_pass_sq.hip); launch_three_pass routes n = 100 there.

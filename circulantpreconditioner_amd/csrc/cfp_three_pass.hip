@@ -14,6 +14,8 @@
 //       register transposes; k_tp_mid: DPP lane permutations; frequencies left bit-reversed),
 //       256-point z DFT, divide by the separable symbol at (kx, k1 + N1 k2, kz), then the same
 //       transforms on the conjugate (inverse)
+//       (k_tp_mid_rec, 256^3 default shape, a transport symbol with |a| <= 1 - 2^-13: the same
+//       array without the z transforms, z solved as the recurrence u_z = a u_{z-1} + w_z)
 //   P3  k_tp_rows<inv>: P1 on the conjugate, x 1/N
 //
 // P1/P3 workgroups are N1 x 16 threads x 16 points with a split-LDS exchange buffer of
@@ -904,6 +906,306 @@ k_tp_mid_sw(cd* data, TPArgs a, int nunits) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// P2 for the transport symbol with z solved by recurrence (k_tp_mid_rec; 256^3, N2 = 8).  The
+// symbol of column (kx, ky) is c + lamz (1 - e^{-2 pi i kz / nz}), c = 1 + colsym: with
+// a = lamz / (c + lamz), "z DFT, divide, inverse z DFT" of v is the cyclic first-order system
+//   u_z = a u_{z-1} + w_z,  w = v nz / (c + lamz)   (nz: the factor the unnormalised pair leaves),
+// solved as u_z = t_z + a^{z+1} t_{nz-1} / (1 - a^nz), t the same recurrence started from zero.
+// The host enables it only where max |a| <= 1 - 2^-13 (cfp_plan.hip); k_tp_mid_sw's output is the
+// same array, so P1 and P3 do not change.
+//
+// The tile is k_tp_mid_sw's (8 x times 8 y2 times 256 z, 128-byte runs, in place).  A thread
+// holds 8 y2 times 2 consecutive z, a wave 8 x times 16 z (lane = x + 8 zl, z = 16 wave + 2 zl + j,
+// slot m = 8 j + y2): the y2 DFT is a register radix-8 and the scan runs thread -> lane bits
+// 3..5 -> waves.  Lane levels: a hypercube scan on xor exchanges (DPP row_ror:8, permlane16 /
+// permlane32 swaps), each level merging (block total S, exclusive prefix X) of two blocks of
+// 2, 4, 8 z with a^2, a^4, a^8.  Wave level: every wave writes its 64 columns' block-end values
+// E_w (16 KiB), one workgroup barrier, then lane (x, zl) forms the carry into its wave for
+// column (x, k2 = zl),
+//   U_{16 w - 1} = sum_k a^{16 k} E_{(w - 1 - k) mod 16} / (1 - a^256)   (Horner in a^16),
+// and the 8 lanes of an x exchange their columns' carries (ds_bpermute).  That barrier is the
+// only one of a unit; the block-end buffer alternates between two units, so a wave that runs
+// ahead writes the next unit's values while others still read this one's.
+//
+// The columns' a and r = 256 / (c + lamz) come from a table that wave 0 fills one unit ahead.
+//
+// PF: slots 0..6 of the next unit come by LDS-DMA into this wave's own 7 KiB, issued as
+// soon as the wave has this unit's values in registers, so they fly for nearly a whole unit; a buffer
+// that is only 8-byte aligned runs without it (global_load_lds_dwordx4 takes 16-byte addresses).
+//
+// The body is a function of __restrict__ pointers to the kernel's LDS arrays: inlined, its LDS
+// reads carry the information that they do not alias the prefetch buffer, without which the
+// compiler waits for every LDS-DMA in flight (vmcnt(0)) before the first LDS read that follows.
+constexpr int kRecNPF = 7;  // slots that come from the LDS prefetch (154 of 160 KiB LDS)
+template <int PROBE, bool PF, int LD>
+__device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPArgs& a, int nunits,
+                                                double* __restrict__ pf_l, cd* __restrict__ carr,
+                                                cd* __restrict__ ctab, cd* __restrict__ tw_l) {
+  constexpr int TN = 256, N2 = 8, N1 = TN / N2, XT = 8, NXT = TN / XT, NW = 16;
+  constexpr int NPF = PF ? kRecNPF : 0;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, x = lane & 7, zl = lane >> 3;
+  const int wv = __builtin_amdgcn_readfirstlane(tid / 64);
+  const i64 zs = (i64)TN << (a.lnyl ? a.lnyl : ilog2(TN));
+  const cd lz = a.lamz;
+  // opaque copy of a lane index: what is derived from it is recomputed at its use instead of
+  // living in a register across the unit (k_tp_mid_sw's idx)
+  const auto idx = [](int i) {
+    asm volatile("" : "+v"(i));
+    return i;
+  };
+  // Column table of unit u: lane c = x + 8 k2 of wave 0 loads the symbol of column (x, k2) and
+  // writes a = lamz / (c + lamz) and r = 256 / (c + lamz), one unit ahead (the unit's barrier
+  // publishes it; three buffers: waves behind that barrier still read the previous unit's).
+  // One division per column and unit instead of one per thread, and no global load inside the
+  // unit, whose wait would also wait for the prefetch in flight.
+  const auto colsym_of = [&](int u) {
+    return a.colsym[(u % NXT) * XT + x + (i64)TN * (a.k1_off + u / NXT + N1 * zl)];
+  };
+  const auto ctab_put = [&](int buf, cd cs) {
+    const cd den = make_cd(cs.x + 1.0 + lz.x, cs.y + lz.y);
+    const double id = 1.0 / fma(den.x, den.x, den.y * den.y);
+    const cd ri = make_cd(den.x * id, -den.y * id);  // 1 / (c + lamz)
+    ctab[(2 * buf) * 64 + idx(lane)] = cmul(lz, ri);
+    ctab[(2 * buf + 1) * 64 + idx(lane)] = make_cd(ri.x * (double)TN, ri.y * (double)TN);
+  };
+  if (tid < TN) tw_l[tid] = a.tw[tid];
+  if (wv == 0 && (int)blockIdx.x < nunits) ctab_put(0, colsym_of((int)blockIdx.x));
+  __syncthreads();
+  // a point's address = a wave-uniform base (unit u = (x tile, local k1): row 8 k1, z = 16 wv;
+  // slot m: row + (m & 7), z + (m >> 3)) + this lane's 32-bit byte offset (x, z = 2 zl): a scalar
+  // base plus one offset register for all 16 slots, instead of 16 address pairs
+  const unsigned loff = 16u * ((unsigned)x + (unsigned)zs * 2u * (unsigned)zl);
+  const auto slot_ptr = [&](int u, int m) {
+    return data + ((u % NXT) * XT + (i64)TN * (N2 * (u / NXT) + (m & 7)) + zs * (16 * wv + (m >> 3)));
+  };
+  const auto at = [](cd* base, unsigned off) { return reinterpret_cast<cd*>(reinterpret_cast<char*>(base) + off); };
+  const auto prefetch = [&](int u) {  // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
+    unsigned lo0 = loff;
+    asm volatile("" : "+s"(u), "+v"(lo0));
+#pragma unroll
+    for (int m = 0; m < NPF; ++m)
+      __builtin_amdgcn_global_load_lds((glb_void_t*)at(slot_ptr(u, m), lo0), (lds_void_t*)(pf_l + (wv * NPF + m) * 128),
+                                       16, 0, (LD & F_NT_LD) ? 2 : 0);
+  };
+  if constexpr (PF) {
+    if ((int)blockIdx.x < nunits) prefetch((int)blockIdx.x);
+  }
+  const bool up3 = (zl & 1) != 0, up4 = (zl & 2) != 0, up5 = (zl & 4) != 0;
+  const cd zero = make_cd(0.0, 0.0), one = make_cd(1.0, 0.0);
+  // pin(): the values are formed where the source forms them.  Sunk towards their uses, a DFT's
+  // or a column's last operations keep their inputs live as well and the kernel goes to scratch.
+  const auto pin = [](cd& w) { asm volatile("" : "+v"(w.x), "+v"(w.y)); };
+  // p q + c in 4 fused operations
+  const auto cfma = [](cd p, cd q, cd c) {
+    return make_cd(fma(p.x, q.x, fma(-p.y, q.y, c.x)), fma(p.x, q.y, fma(p.y, q.x, c.y)));
+  };
+
+  // One unit.  MORE: another unit follows (its prefetch and column table are issued here); the
+  // last unit is its own instantiation, so that every wait inside a unit knows what is in flight.
+  int par = 0, buf = 0;
+  const auto unit = [&](const int it, auto more_c) {
+    constexpr bool more = decltype(more_c)::value;
+    const int u = it;
+    const int k1 = a.k1_off + u / NXT;  // global k1
+    const int nbuf = buf == 2 ? 0 : buf + 1;
+    cd v[16], csn = zero;
+    if constexpr (PROBE & PR_NO_LOAD) {
+#pragma unroll
+      for (int m = 0; m < 16; ++m) v[m] = make_cd(lane + m, wv + u);
+    } else {
+      if constexpr (PF) {
+        // this wave's DMA landed (and its stores of the previous unit: leaving those in flight
+        // behind a vmcnt(16) measured 0.7 % slower, profiles/r07_zrec_ab.txt)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int m = 0; m < NPF; ++m)
+          v[m] = fromv(*reinterpret_cast<const dv2*>(pf_l + (wv * NPF + m) * 128 + 2 * idx(lane)));
+      }
+      if constexpr (more) csn = colsym_of(it + (int)gridDim.x);  // every wave loads (no wait at a join), wave 0 uses it
+      {
+        int ul = u;
+        unsigned lo1 = loff;
+        asm volatile("" : "+s"(ul), "+v"(lo1));  // scalar base + this register, formed here
+#pragma unroll
+        for (int m = NPF; m < 16; ++m) v[m] = gload<LD>(at(slot_ptr(ul, m), lo1));
+      }
+    }
+    if (more && wv == 0) ctab_put(nbuf, csn);
+    // twiddle W_256^{y2 k1} (uniform over the workgroup), then the y2 DFT: natural order in and out
+#pragma unroll
+    for (int y = 1; y < N2; ++y) {
+      const cd w = tw_l[(y * k1) & (TN - 1)];
+      v[y] = cmul(v[y], w);
+      v[8 + y] = cmul(v[8 + y], w);
+    }
+    // The next unit's prefetch, once every load of this one has landed (pin: the values are in
+    // their registers, so the prefetch buffer is free as well).  While an LDS-DMA is in flight
+    // the compiler turns every wait for a global load into vmcnt(0), the DMA included: issued
+    // before the loads are consumed it would be drained at their first use.  From here it flies
+    // until the next unit's top.
+    if constexpr (PF && more && !(PROBE & PR_NO_LOAD)) {
+#pragma unroll
+      for (int m = 0; m < 16; ++m) pin(v[m]);
+      prefetch(it + (int)gridDim.x);
+    }
+    // (the scheduling barriers keep one DFT's, one column's, one level's temporaries live at a time)
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (!(PROBE & PR_NO_Y2)) {
+      dft_reg<8>(v);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) pin(v[m]);
+      __builtin_amdgcn_sched_barrier(0);
+      dft_reg<8>(v + 8);
+#pragma unroll
+      for (int m = 8; m < 16; ++m) pin(v[m]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (!(PROBE & PR_NO_ZMATH)) {
+      const auto pow2zl = [&](cd aa) {  // a^{2 zl}
+        cd pw = cmul(aa, aa), q = up3 ? pw : one;
+        pw = cmul(pw, pw);
+        q = up4 ? cmul(q, pw) : q;
+        pw = cmul(pw, pw);
+        return up5 ? cmul(q, pw) : q;
+      };
+#pragma unroll
+      for (int k2 = 0; k2 < 8; ++k2) {
+        const int c = (idx(lane) & 7) + 8 * k2;
+        const cd aa = ctab[(2 * buf) * 64 + c], r = ctab[(2 * buf + 1) * 64 + c];
+        const cd v0 = cmul(v[k2], r), v1 = cmul(v[8 + k2], r);
+        // thread total, then the lane levels: S = block total, X = value at the end of the
+        // previous thread (block-local, zero start); pw = a^2, a^4, a^8 and q = a^{2 (zl & 1)},
+        // a^{2 (zl & 3)}, each formed at its level
+        cd S = cfma(aa, v0, v1), X, lo, hi, pw = cmul(aa, aa), q;
+        __builtin_amdgcn_sched_barrier(0);
+        {
+          const cd pr = lane_xor8(S);
+          lo = up3 ? pr : S;
+          hi = up3 ? S : pr;
+          X = up3 ? lo : zero;
+          S = cfma(pw, lo, hi);
+          q = up3 ? pw : one;
+          pw = cmul(pw, pw);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+          lo = S;
+          hi = S;
+          swap_c<4>(lo, hi);
+          if (up4) X = cfma(q, lo, X);
+          S = cfma(pw, lo, hi);
+          q = up4 ? cmul(q, pw) : q;
+          pw = cmul(pw, pw);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+          lo = S;
+          hi = S;
+          swap_c<5>(lo, hi);
+          if (up5) X = cfma(q, lo, X);
+          S = cfma(pw, lo, hi);  // the wave's block-end value, in every lane
+        }
+        v[k2] = cfma(aa, X, v0);  // the wave-local solution (zero carry into the wave)
+        v[8 + k2] = cfma(aa, v[k2], v1);
+        pin(v[k2]);
+        pin(v[8 + k2]);
+        if (zl == k2) carr[(par * NW + wv) * 64 + idx(lane)] = S;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      lds_barrier();  // the unit's only barrier: every wave's block-end values are in carr[par]
+      cd cin;  // the carry into this wave for column (x, k2 = zl)
+      {
+        const int ln = idx(lane);
+        const cd am = ctab[(2 * buf) * 64 + ln];
+        const cd am2 = cmul(am, am), am4 = cmul(am2, am2), am8 = cmul(am4, am4);
+        const cd A = cmul(am8, am8);  // a^16
+        cd acc = carr[(par * NW + wv) * 64 + ln];
+#pragma unroll
+        for (int k = 14; k >= 0; --k) {
+          acc = cfma(acc, A, carr[(par * NW + ((wv - 1 - k) & 15)) * 64 + ln]);
+          if ((k & 3) == 0) __builtin_amdgcn_sched_barrier(0);  // 4 reads in flight, not 16 (64 VGPRs)
+        }
+        const cd A2 = cmul(A, A), A4 = cmul(A2, A2), A8 = cmul(A4, A4), A16 = cmul(A8, A8);
+        const cd d = make_cd(1.0 - A16.x, -A16.y);
+        const double id = 1.0 / fma(d.x, d.x, d.y * d.y);
+        cin = make_cd(fma(acc.x, d.x, acc.y * d.y) * id, fma(acc.y, d.x, -acc.x * d.y) * id);
+      }
+#pragma unroll
+      for (int k2 = 0; k2 < 8; ++k2) {
+        const int c = (idx(lane) & 7) + 8 * k2;
+        const long long bx = __double_as_longlong(cin.x), by = __double_as_longlong(cin.y);
+        const unsigned xl = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(bx & 0xffffffffll));
+        const unsigned xh = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(bx >> 32));
+        const unsigned yl = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(by & 0xffffffffll));
+        const unsigned yh = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(by >> 32));
+        const cd ci = make_cd(__longlong_as_double((long long)(((unsigned long long)xh << 32) | xl)),
+                              __longlong_as_double((long long)(((unsigned long long)yh << 32) | yl)));
+        // weights a^{2 zl + 1}, a^{2 zl + 2} of the carry at this thread's two z, rebuilt from
+        // the column's a (kept across the barrier they cost 64 VGPRs)
+        const cd aa = ctab[(2 * buf) * 64 + c];
+        const cd g = cmul(cmul(aa, pow2zl(aa)), ci);
+        v[k2] = cadd(v[k2], g);
+        v[8 + k2] = cfma(aa, g, v[8 + k2]);
+        pin(v[k2]);
+        pin(v[8 + k2]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // inverse y2 DFT on the conjugate, conjugate twiddle, store
+#pragma unroll
+    for (int m = 0; m < 16; ++m) v[m] = cconj(v[m]);
+    if constexpr (!(PROBE & PR_NO_Y2)) {
+      dft_reg<8>(v);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) pin(v[m]);
+      __builtin_amdgcn_sched_barrier(0);
+      dft_reg<8>(v + 8);
+#pragma unroll
+      for (int m = 8; m < 16; ++m) pin(v[m]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    {
+      // opaque copies: the twiddles are read again and the addresses formed again, instead of
+      // living in registers since the loads
+      int k1s = k1, us = u;
+      unsigned lo2 = loff;
+      asm volatile("" : "+s"(k1s), "+s"(us), "+v"(lo2));
+      if constexpr (PROBE & PR_NO_STORE) {
+        double acc = 0.0;
+#pragma unroll
+        for (int m = 0; m < 16; ++m) acc += v[m].x + v[m].y;
+        if (acc == 1.2345e300) *at(slot_ptr(us, 0), lo2) = make_cd(acc, 0.0);  // keeps the work live, never true
+      } else {
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+          const cd w = (m & 7) ? tw_l[((m & 7) * k1s) & (TN - 1)] : one;
+          gstore<0>(at(slot_ptr(us, m), lo2), cconj(cmul(v[m], w)));
+        }
+      }
+    }
+    par ^= 1;
+    buf = nbuf;
+  };
+  int it = blockIdx.x;
+  for (; it + (int)gridDim.x < nunits; it += gridDim.x) unit(it, std::true_type{});
+  if (it < nunits) unit(it, std::false_type{});
+}
+
+template <int PROBE = 0, bool PF = false, int LD = 0, int TAG = 0>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
+k_tp_mid_rec(cd* data, TPArgs a, int nunits) {
+#ifndef CFP_KEXP
+  static_assert(PROBE == 0, "timing probes are built in tools/kexp only");
+#endif
+  __shared__ __attribute__((aligned(16))) double pf_l[PF ? 16 * kRecNPF * 128 : 2];
+  __shared__ __attribute__((aligned(16))) cd carr[2 * 16 * 64];  // block-end values [unit parity][wave][column]
+  __shared__ __attribute__((aligned(16))) cd ctab[3 * 2 * 64];   // the columns' a and r [unit mod 3][a, r][column]
+  __shared__ cd tw_l[256];  // the twiddles: a global load after the kernel's own stores is a vector load
+  tp_mid_rec_body<PROBE, PF, LD>(data, a, nunits, pf_l, carr, ctab, tw_l);
+}
+
 
 bool three_pass_supported(const i64 n[3]) {
   return n[0] == n[1] && n[1] == n[2] && (n[0] == 128 || n[0] == 256 || n[0] == 512);
@@ -1299,6 +1601,17 @@ static void launch_mid_sw(cd* data, const TPArgs& a, hipStream_t s) {
             dim3(T * (TN / 16)), s, data, a, units);
 }
 
+// the recurrence P2 (k_tp_mid_rec): 256^3, default shape, an eligible transport symbol (a.zrec);
+// TAG 1 inside the stand-in KSP, as launch_mid_sw
+template <bool PF>
+static void launch_mid_rec(cd* data, const TPArgs& a, hipStream_t s) {
+  constexpr int units = (256 / 8) * (256 / 8);  // x tiles x k1
+  if (a.krylov)
+    TP_LAUNCH((k_tp_mid_rec<0, PF, kP2LoadFlags, 1>), dim3(grid_of(units, 1)), dim3(1024), s, data, a, units);
+  else
+    TP_LAUNCH((k_tp_mid_rec<0, PF, kP2LoadFlags>), dim3(grid_of(units, 1)), dim3(1024), s, data, a, units);
+}
+
 bool three_pass_slab_supported(const i64 n[3], int P) {
   // N1 = 32 rows per P1 unit, k1 split over the ranks (P | 32); P3 reads chunk rows N2 apart
   // per thread and N2 TY = 2 N2 apart per slot (nyl >= 2 N2: 256^3 N2 = 8, 512^3 N2 = 16)
@@ -1399,6 +1712,10 @@ hipError_t launch_three_pass_fused(int stage, int n, const cd* in, cd* out, cons
   if (gx) launch_rows_fused<true>(stage, in, out, a, s, g);
   else launch_rows_fused<false>(stage, in, out, a, s, g);
   return hipGetLastError();
+}
+
+bool three_pass_zrec_shape(int n, TPShape shape) {
+  return n == 256 && shape.mid == TP_MID_DEFAULT && (shape.n1 == 0 || shape.n1 == 32);
 }
 
 bool three_pass_shape_valid(int n1, int mid, i64 n) {
@@ -1530,7 +1847,12 @@ hipError_t launch_three_pass(int stage, int n, const cd* in, cd* out, const TPAr
     return hipGetLastError();
   }
   if (stage == 1) {
-    if ((shape.mid == TP_MID_SWAP64_PF || shape.mid == TP_MID_DEFAULT) && pf_ok) {
+    // an eligible transport symbol under the default shape: z by recurrence (k_tp_mid_rec);
+    // swap64_pf stays the FFT kernel for a same-process A/B
+    if (a.zrec && three_pass_zrec_shape(n, shape)) {
+      if (pf_ok) launch_mid_rec<true>(out, a, s);
+      else launch_mid_rec<false>(out, a, s);
+    } else if ((shape.mid == TP_MID_SWAP64_PF || shape.mid == TP_MID_DEFAULT) && pf_ok) {
       if (n1 == 64) launch_mid_sw<4, 256, true>(out, a, s);
       else launch_mid_sw<8, 256, true>(out, a, s);
     } else if (shape.mid == TP_MID_SWAP64 || shape.mid == TP_MID_SWAP64_PF || shape.mid == TP_MID_DEFAULT) {

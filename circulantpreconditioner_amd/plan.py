@@ -246,7 +246,8 @@ class CirculantPlan:
 
     def set_three_pass_shape(self, n1: int = 0, mid: str | int = "default") -> "CirculantPlan":
         """Kernel shape of the 256^3 3-sweep schedule (tests / measurements): the y split n1
-        (0 = default, 32 or 64) and the middle kernel ('default' = 'swap64pf', 'lane64', 'lane32',
+        (0 = default, 32 or 64) and the middle kernel ('default' = 'swap64pf', or the z recurrence
+        where the symbol allows it, see mid_kernel(); 'lane64', 'lane32',
         'swap64': the y2 DFT on permlane register transposes, 64-column tile; 'swap64pf': the
         same with an LDS-DMA prefetch of half the next unit; 'blocked': 'swap64pf' with the
         blocked intermediate layout, 1 KiB P2 runs; 'blocked32': blocks of 4 x and the permlane
@@ -272,6 +273,13 @@ class CirculantPlan:
             out.append({"axis": PASS_AXES[ax.value], "n": nn.value, "ncols": nc.value,
                         "mode": PASS_MODES[mode.value], "fast": bool(fast.value)})
         return out
+
+    def mid_kernel(self) -> str:
+        """The middle kernel the next apply launches: 'zrec' (z by recurrence: 256^3, default
+        shape, a transport symbol with z ratio <= 1 - 2^-13) or 'fft'."""
+        k = ctypes.c_int()
+        check(lib().cfp_plan_mid_kernel(self._h, ctypes.byref(k)))
+        return "zrec" if k.value == 1 else "fft"
 
     def time_passes(self, b: torch.Tensor, x: torch.Tensor, iters: int = 20, stream=None) -> list:
         """Mean device time (ms) of each launch of one apply, HIP events on `stream`."""

@@ -170,7 +170,8 @@ int cfp_plan_set_graph(cfp_plan_t plan, int on);
 int cfp_plan_set_schedule(cfp_plan_t plan, int schedule);
 /* Kernel shape of the 3-sweep schedule at 256^3, for tests and measurements (0, 0 = the
  * measured default; the shape never changes the result beyond rounding).  n1: the y split
- * ny = n1 * (256 / n1), 0 (default), 32 or 64.  mid: the middle kernel, 0 (default = SWAP64_PF),
+ * ny = n1 * (256 / n1), 0 (default), 32 or 64.  mid: the middle kernel, 0 (default = SWAP64_PF, or
+ * the z recurrence for an eligible transport symbol, see cfp_plan_mid_kernel),
  * CFP_TP_MID_LANE64 (y2 DFT across lanes, 64-column tile), CFP_TP_MID_LANE32 (32-column tile) or
  * CFP_TP_MID_SWAP64 (y2 DFT on v_permlane32/16_swap register transposes, 64-column tile;
  * 256^3 only, 128^3 keeps its default).  Other values: CFP_ERR_ARG_OUTOFRANGE. */
@@ -180,6 +181,13 @@ int cfp_plan_set_schedule(cfp_plan_t plan, int schedule);
 #define CFP_TP_MID_SWAP64 3
 #define CFP_TP_MID_SWAP64_PF 4 /* SWAP64 + LDS-DMA prefetch of half the next unit */
 int cfp_plan_set_three_pass_shape(cfp_plan_t plan, int n1, int mid);
+/* The middle kernel the plan's next apply launches: 0 the FFT kernel (or a schedule without a
+ * middle kernel), CFP_MID_KERNEL_ZREC the z recurrence.  The recurrence runs at 256^3 under the
+ * default shape for a symbol set by cfp_plan_set_symbol_transport whose z ratio
+ * (cfp_transport_z_ratio) is at most 1 - 2^-13; CFP_TP_MID_SWAP64_PF is the FFT kernel always. */
+#define CFP_MID_KERNEL_FFT 0
+#define CFP_MID_KERNEL_ZREC 1
+int cfp_plan_mid_kernel(cfp_plan_t plan, int *kind);
 
 /* Introspection: number of kernel launches of one apply, and per-launch timing.
  * cfp_plan_time_passes runs `iters` applies and writes the mean duration (ms) of each of the
@@ -209,6 +217,10 @@ int cfp_build_diag_3d(double *diag_dev, const double *cx_hat_dev, const double *
                       void *stream);
 /* host: out[k] = DFT(1, -1, 0, ...)[k] = 1 - e^{-2 pi i k/n} (0 for n == 1), n complex values */
 int cfp_transport_symbol_1d(int64_t n, double *out_host);
+/* host (no GPU needed): max over (kx, ky) of |lam_z / (1 + s_x[kx] + s_y[ky] + lam_z)| with
+ * s_d = lam_d * cfp_transport_symbol_1d(n_d): along z the transport symbol is the first-order
+ * recurrence u_z = a u_{z-1} + w_z with that ratio a per column.  Infinity if a denominator is 0. */
+int cfp_transport_z_ratio(int64_t nx, int64_t ny, const double lam[6], double *amax_host);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,10 @@ NAMES = {32: "full, s_setprio 1 on the second half of the waves", 0: "full (prod
          7: "mem only (no math, no exchanges)", 8: "no loads", 16: "no stores", 24: "no loads, no stores (compute+xchg)",
          26: "no mem, no z math (y2 + xchg)", 28: "no mem, no xchg (y2 + z math)", 29: "no mem, no xchg, no y2 (z math)",
          30: "no mem, no xchg, no z math (y2 only)", 31: "nothing (loop + twiddle)"}
-cases = [0, 32, 100, 1, 2, 3, 4, 6, 7, 8, 16, 24, 26, 28, 29, 30, 31, 1000, 1007]
+NAMES.update({200: "zrec: full (k_tp_mid_rec + prefetch)", 201: "zrec: no y2 DFT", 202: "zrec: no scan", 203: "zrec: no y2, no scan (mem + twiddle)",
+              208: "zrec: no loads", 216: "zrec: no stores", 224: "zrec: no loads, no stores (compute)",
+              227: "zrec: nothing (loop + twiddle)"})
+cases = [0, 32, 100, 1, 2, 3, 4, 6, 7, 8, 16, 24, 26, 28, 29, 30, 31, 1000, 1007, 200, 201, 202, 203, 208, 216, 224, 227]
 res = {c: [] for c in cases}
 for rnd in range(3):
     for c in cases:

@@ -4,6 +4,8 @@
 // the whole grid with the product's persistent grid (one 1024-thread workgroup per CU).
 //   which < 64:  k_tp_mid_sw<64, 8, 256, which>   (PR_* bits of cfp_three_pass.hip)
 //   which = 100: k_tp_mid<0, 64, 8, 256> (the DPP lane-DFT kernel)
+//   which = 200 + P: k_tp_mid_rec<P> (the recurrence kernel; P = PR_NO_Y2 | PR_NO_ZMATH (no scan)
+//                | PR_NO_LOAD | PR_NO_STORE), lambda_z = 0.02
 //   which += 1000: one workgroup per unit instead of the persistent grid
 #define CFP_KEXP 1
 #include "cfp_three_pass.hip"
@@ -23,6 +25,14 @@ static void launch_sw(cd* d, const TPArgs& a, unsigned g) {
   hipLaunchKernelGGL((k_tp_mid_sw<64, 8, 256, P, true, 256, 0, F_NT_LD>), dim3(g), dim3(1024), 0, 0, d, a, 1024);
 }
 
+// the recurrence P2 (LDS-DMA prefetch, non-temporal loads) with probe bits P
+template <int P>
+static void launch_rec(cd* d, TPArgs a, unsigned g) {
+  a.zrec = 1;
+  a.lamz = make_cd(0.02, 0.0);
+  hipLaunchKernelGGL((k_tp_mid_rec<P, true, F_NT_LD>), dim3(g), dim3(1024), 0, 0, d, a, 1024);
+}
+
 extern "C" int tp_probe(int which, void* data, const void* tw, const void* colsym, const void* axsym, int iters,
                         float* ms) {
   TPArgs a;
@@ -37,6 +47,9 @@ extern "C" int tp_probe(int which, void* data, const void* tw, const void* colsy
     switch (which) {
 #define C(P) case P: launch_sw<P>(d, a, g); return 0;
       C(0) C(1) C(2) C(3) C(4) C(6) C(7) C(8) C(16) C(24) C(26) C(28) C(29) C(30) C(31) C(32)
+#undef C
+#define C(P) case 200 + P: launch_rec<P>(d, a, g); return 0;
+      C(0) C(1) C(2) C(3) C(8) C(16) C(24) C(27)
 #undef C
       case 100: hipLaunchKernelGGL((k_tp_mid<0, 64, 8, 256>), dim3(g), dim3(1024), 0, 0, d, a, 1024); return 0;
       default: return 1;
