@@ -66,6 +66,17 @@ class TransportResult(ctypes.Structure):
         return d
 
 
+class AIJInfo(ctypes.Structure):
+    """PetscMiniAIJInfo (include/petsc_mini.h): the device form an AIJ's MatMult will use."""
+    _fields_ = [("format", ctypes.c_int), ("B", ctypes.c_int), ("nd", ctypes.c_int), ("ncls", ctypes.c_int),
+                ("nblk", ctypes.c_int), ("re", ctypes.c_int), ("lds_bytes", ctypes.c_int64)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_}
+        d["format"] = {0: "csr", 1: "dia", 2: "bdia"}[d["format"]]
+        return d
+
+
 class WaveConfig(ctypes.Structure):
     """cfp_wave_config (include/wave_system.h)."""
     _fields_ = [("nx", ctypes.c_int64), ("ny", ctypes.c_int64), ("nz", ctypes.c_int64),
@@ -161,6 +172,7 @@ def declare(L) -> None:
         "PetscMiniAllreduce": ([c_int, P(ctypes.c_double), i64, c_int], c_int),
         "PetscMiniCommGetNCCL": ([c_int, P(vp)], c_int),
         "PetscMiniMatAIJGetFormat": ([vp, P(c_int)], c_int),
+        "PetscMiniMatAIJDescribe": ([vp, P(AIJInfo)], c_int),
         "VecCreateMPI": ([c_int, i64, i64, P(vp)], c_int),
         "VecCreateMPIHIP": ([c_int, i64, i64, P(vp)], c_int),
         "VecCreateMPIHIPWithArray": ([c_int, i64, i64, i64, vp, P(vp)], c_int),
@@ -230,6 +242,10 @@ def declare(L) -> None:
         "PCDestroy": ([P(vp)], c_int),
         "VecMDot": ([vp, i64, P(vp), P(S)], c_int),
         "VecMAXPY": ([vp, i64, P(S), P(vp)], c_int),
+        "VecMiniMAXPYNorm": ([vp, i64, P(S), P(vp), c_int, P(ctypes.c_double)], c_int),
+        "VecMiniMDotMAXPYNorm": ([vp, i64, P(ctypes.c_double), P(vp), P(S), P(ctypes.c_double)], c_int),
+        "VecMiniMAXPYNormDeviceDots": ([vp, i64, P(ctypes.c_double), P(vp), vp, P(S), P(ctypes.c_double)], c_int),
+        "PetscMiniDeviceRead": ([vp, i64, P(ctypes.c_double)], c_int),
         "KSPCreate": ([c_int, P(vp)], c_int),
         "KSPSetType": ([vp, cs], c_int),
         "KSPSetTolerances": ([vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, i64], c_int),

@@ -44,6 +44,8 @@ struct DiaDesc {
   i64 off[DIA_MAX];
   int nd = 0, ncls = 0;
 };
+// the dynamic LDS of a row-class launch: the classes' table and their mask bytes
+inline size_t dia_lds_bytes(size_t scalar_bytes, int ncls, int nd) { return scalar_bytes * (size_t)(ncls * nd) + 256; }
 hipError_t blas_dia_spmv(i64 m, const DiaDesc& d, const unsigned char* cls, const unsigned char* masks, const cd* tab,
                          const cd* x, cd* y, hipStream_t s);
 hipError_t blas_dia_spmv(i64 m, const DiaDesc& d, const unsigned char* cls, const unsigned char* masks,
@@ -63,6 +65,14 @@ struct BDiaDesc {
   int re = 0;  // 1: every table entry has a zero imaginary part (the wave operator): real x complex products
 };
 #define BDIA_LDS_MAX (60 * 1024)
+// The dynamic LDS a block-form launch asks for: per block its B x B table entries and one bnz
+// word, plus the mask and cbase arrays of 256 classes.  The launcher (blas_bdia_spmv) and the
+// builder that admits a table (petsc_mini.cpp, aij_build_bdia_b) share this formula and its limit,
+// so every matrix stored in the block form can be multiplied.
+#define BDIA_LDS_LIMIT (BDIA_LDS_MAX + 2048)
+inline size_t bdia_lds_bytes(size_t scalar_bytes, int B, size_t nblk) {
+  return (scalar_bytes * (size_t)(B * B) + sizeof(unsigned)) * nblk + 2 * sizeof(unsigned short) * 256;
+}
 hipError_t blas_bdia_spmv(i64 mb, const BDiaDesc& d, const unsigned char* cls, const unsigned short* masks,
                           const unsigned short* cbase, const unsigned* bnz, const cd* tab, const cd* x, cd* y,
                           hipStream_t s);

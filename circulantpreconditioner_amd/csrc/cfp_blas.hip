@@ -746,7 +746,7 @@ static hipError_t dia_t(i64 m, const DiaDesc& d, const unsigned char* cls, const
                         const T* x, T* y, hipStream_t s) {
   if (m <= 0) return hipSuccess;
   if (d.nd < 1 || d.nd > DIA_MAX || d.ncls < 1 || d.ncls > 256) return hipErrorInvalidValue;
-  const size_t lds = sizeof(T) * (size_t)(d.ncls * d.nd) + 256;
+  const size_t lds = dia_lds_bytes(sizeof(T), d.ncls, d.nd);
   blaunch(1, k_dia_spmv<T>, dim3(nblocks(m)), dim3(BLAS_THREADS), lds, s, m, d, cls, masks, tab, x, y);
   return hipGetLastError();
 }
@@ -766,8 +766,8 @@ static hipError_t bdia_t(i64 mb, const BDiaDesc& d, const unsigned char* cls, co
   if (mb <= 0) return hipSuccess;
   if (d.nd < 1 || d.nd > BDIA_MAX || d.ncls < 1 || d.ncls > 256 || d.B < 2 || d.B > 4 || d.nblk < 1)
     return hipErrorInvalidValue;
-  const size_t lds = (sizeof(T) * d.B * d.B + sizeof(unsigned)) * (size_t)d.nblk + 2 * sizeof(unsigned short) * 256;
-  if (lds > BDIA_LDS_MAX + 2048) return hipErrorInvalidValue;
+  const size_t lds = bdia_lds_bytes(sizeof(T), d.B, (size_t)d.nblk);
+  if (lds > BDIA_LDS_LIMIT) return hipErrorInvalidValue;
   // persistent grid: each workgroup stages the class table into LDS once (tens of KB), so a
   // workgroup per 256 cells would re-read it ~8,000 times at 128^3.  512-thread workgroups, as
   // many per CU as the table's LDS allows (at most 3: 24 waves, the kernel's ~70 VGPRs allow 28)

@@ -1336,8 +1336,9 @@ static bool aij_build_dia(Mat M, cfp::DiaDesc* d, std::vector<unsigned char>* cl
 // Block row-class form of the host CSR (cfp_blas.h, k_bdia_spmv), tried when the row-class form
 // does not fit: the matrix cut into B x B blocks (B = 2, 3, 4), every nonzero block on one of at
 // most BDIA_MAX block diagonals (a 3-D periodic stencil has 13), at most 256 distinct block
-// rows, their present blocks within the LDS budget.  The interleaved wave operator
-// (wave_system.cpp: d + 1 unknowns per cell, a 2d + 1 cell stencil) qualifies with B = d + 1.  Among the block sizes that fit, the one with the fewest
+// rows, their present blocks within the launcher's LDS limit (cfp::bdia_lds_bytes, cfp_blas.h).
+// The interleaved wave operator (wave_system.cpp: d + 1 unknowns per cell, a 2d + 1 cell
+// stencil) qualifies with B = d + 1.  Among the block sizes that fit, the one with the fewest
 // multiply-adds per row (nd B) wins; the product is the same up to summation order.
 static bool aij_build_bdia_b(Mat M, int B, cfp::BDiaDesc* d, std::vector<unsigned char>* cls,
                              std::vector<unsigned short>* masks, std::vector<unsigned short>* cbase,
@@ -1357,7 +1358,6 @@ static bool aij_build_bdia_b(Mat M, int B, cfp::BDiaDesc* d, std::vector<unsigne
   std::sort(offs.begin(), offs.end());
   const int nd = (int)offs.size(), bs = nd * B * B;
   const size_t per_cls = sizeof(VS) * (size_t)bs;
-  const size_t blk_bytes = sizeof(VS) * (size_t)(B * B);
   cls->assign((size_t)mb, 0);
   masks->clear();
   std::vector<VS> dense;  // classes' rows, dense over all nd diagonals (for the comparison)
@@ -1394,7 +1394,7 @@ static bool aij_build_bdia_b(Mat M, int B, cfp::BDiaDesc* d, std::vector<unsigne
     }
     if (c < 0) {
       nblk += (size_t)__builtin_popcount(mk);
-      if (masks->size() == 256 || nblk * blk_bytes > BDIA_LDS_MAX) return false;
+      if (masks->size() == 256 || cfp::bdia_lds_bytes(sizeof(VS), B, nblk) > BDIA_LDS_LIMIT) return false;
       c = (int)masks->size();
       masks->push_back((unsigned short)mk);
       dense.insert(dense.end(), row.begin(), row.end());
@@ -1481,60 +1481,67 @@ static void aij_free_device(Mat M) {
   M->xloc_len = -1;
 }
 
-// the device copy: the row-class diagonal form when the matrix has one, else the CSR (once;
-// MatShift rebuilds it)
+// The device form of the host CSR, chosen on the host: the row-class diagonal form when the matrix
+// has one, else the block row-class form, else CSR.  aij_upload copies the choice to the device;
+// PetscMiniMatAIJDescribe reports it.
+struct AijForm {
+  int format = 0;  // 0 csr, 1 dia, 2 bdia
+  cfp::DiaDesc dia{};
+  std::vector<unsigned char> cls, dia_mask;
+  cfp::BDiaDesc bdia{};
+  std::vector<unsigned short> masks, cbase;
+  std::vector<unsigned> bnz;
+  std::vector<VS> tab;
+};
+static void aij_select(Mat M, AijForm* f) {
+  f->format = 0;
+  if (aij_build_dia(M, &f->dia, &f->cls, &f->dia_mask, &f->tab)) f->format = 1;
+  else if (aij_build_bdia(M, &f->bdia, &f->cls, &f->masks, &f->cbase, &f->bnz, &f->tab)) f->format = 2;
+}
+
+// the device copy in the form aij_select chose (once; MatShift rebuilds the class forms)
 static PetscErrorCode aij_upload(Mat M) {
   if (M->rowptr || M->dia == 1 || M->bdia == 1) return PETSC_SUCCESS;
-  if (M->dia < 0) {
-    std::vector<unsigned char> cls, masks;
-    std::vector<VS> tab;
-    cfp::DiaDesc d{};
-    M->dia = aij_build_dia(M, &d, &cls, &masks, &tab) ? 1 : 0;
-    if (M->dia == 1) {
-      hipError_t e = hipMalloc(&M->dia_cls, cls.size());
-      if (e == hipSuccess) e = hipMalloc(&M->dia_mask, masks.size());
-      if (e == hipSuccess) e = hipMalloc(&M->dia_tab, sizeof(VS) * tab.size());
-      if (e == hipSuccess) e = hipMemcpy(M->dia_cls, cls.data(), cls.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(M->dia_mask, masks.data(), masks.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(M->dia_tab, tab.data(), sizeof(VS) * tab.size(), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        aij_free_device(M);
-        return ERR(PETSC_ERR_MEM, hipGetErrorString(e));
-      }
-      M->dia_d = d;
-      M->h_cls.swap(cls);
-      M->h_mask.swap(masks);
-      M->xloc_len = -1;
-      return PETSC_SUCCESS;
+  AijForm f;
+  aij_select(M, &f);
+  M->dia = f.format == 1 ? 1 : 0;
+  M->bdia = f.format == 2 ? 1 : 0;
+  if (f.format == 1) {
+    hipError_t e = hipMalloc(&M->dia_cls, f.cls.size());
+    if (e == hipSuccess) e = hipMalloc(&M->dia_mask, f.dia_mask.size());
+    if (e == hipSuccess) e = hipMalloc(&M->dia_tab, sizeof(VS) * f.tab.size());
+    if (e == hipSuccess) e = hipMemcpy(M->dia_cls, f.cls.data(), f.cls.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(M->dia_mask, f.dia_mask.data(), f.dia_mask.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(M->dia_tab, f.tab.data(), sizeof(VS) * f.tab.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      aij_free_device(M);
+      return ERR(PETSC_ERR_MEM, hipGetErrorString(e));
     }
+    M->dia_d = f.dia;
+    M->h_cls.swap(f.cls);
+    M->h_mask.swap(f.dia_mask);
+    M->xloc_len = -1;
+    return PETSC_SUCCESS;
   }
-  if (M->bdia < 0) {
-    std::vector<unsigned char> cls;
-    std::vector<unsigned short> masks, cbase;
-    std::vector<unsigned> bnz;
-    std::vector<VS> tab;
-    cfp::BDiaDesc d{};
-    M->bdia = aij_build_bdia(M, &d, &cls, &masks, &cbase, &bnz, &tab) ? 1 : 0;
-    if (M->bdia == 1) {
-      const size_t mb = sizeof(unsigned short) * masks.size();
-      hipError_t e = hipMalloc(&M->bdia_cls, cls.size());
-      if (e == hipSuccess) e = hipMalloc(&M->bdia_mask, mb);
-      if (e == hipSuccess) e = hipMalloc(&M->bdia_cbase, mb);
-      if (e == hipSuccess) e = hipMalloc(&M->bdia_bnz, sizeof(unsigned) * bnz.size());
-      if (e == hipSuccess)
-        e = hipMemcpy(M->bdia_bnz, bnz.data(), sizeof(unsigned) * bnz.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMalloc(&M->bdia_tab, sizeof(VS) * tab.size());
-      if (e == hipSuccess) e = hipMemcpy(M->bdia_cls, cls.data(), cls.size(), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(M->bdia_mask, masks.data(), mb, hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(M->bdia_cbase, cbase.data(), mb, hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(M->bdia_tab, tab.data(), sizeof(VS) * tab.size(), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        aij_free_device(M);
-        return ERR(PETSC_ERR_MEM, hipGetErrorString(e));
-      }
-      M->bdia_d = d;
-      return PETSC_SUCCESS;
+  if (f.format == 2) {
+    const size_t mb = sizeof(unsigned short) * f.masks.size();
+    hipError_t e = hipMalloc(&M->bdia_cls, f.cls.size());
+    if (e == hipSuccess) e = hipMalloc(&M->bdia_mask, mb);
+    if (e == hipSuccess) e = hipMalloc(&M->bdia_cbase, mb);
+    if (e == hipSuccess) e = hipMalloc(&M->bdia_bnz, sizeof(unsigned) * f.bnz.size());
+    if (e == hipSuccess)
+      e = hipMemcpy(M->bdia_bnz, f.bnz.data(), sizeof(unsigned) * f.bnz.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&M->bdia_tab, sizeof(VS) * f.tab.size());
+    if (e == hipSuccess) e = hipMemcpy(M->bdia_cls, f.cls.data(), f.cls.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(M->bdia_mask, f.masks.data(), mb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(M->bdia_cbase, f.cbase.data(), mb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(M->bdia_tab, f.tab.data(), sizeof(VS) * f.tab.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      aij_free_device(M);
+      return ERR(PETSC_ERR_MEM, hipGetErrorString(e));
     }
+    M->bdia_d = f.bdia;
+    return PETSC_SUCCESS;
   }
   const size_t nnz = M->h_col.size();
   hipError_t e = hipMalloc(&M->rowptr, sizeof(i64) * (size_t)(M->m + 1));
@@ -1550,6 +1557,30 @@ static PetscErrorCode aij_upload(Mat M) {
     M->rowptr = M->col = nullptr;
     M->val = nullptr;
     return ERR(PETSC_ERR_MEM, hipGetErrorString(e));
+  }
+  return PETSC_SUCCESS;
+}
+extern "C" PetscErrorCode PetscMiniMatAIJDescribe(Mat A, PetscMiniAIJInfo* info) {
+  MCHK(A);
+  if (!info) return ERR(PETSC_ERR_ARG_NULL, "NULL output");
+  if (A->type == MATMPIAIJ && A->dblk) A = A->dblk;  // the diagonal block carries the device form
+  if (A->type != MATSEQAIJ || A->building) return ERR(PETSC_ERR_ARG_WRONG, "not an assembled AIJ");
+  AijForm f;
+  aij_select(A, &f);
+  *info = PetscMiniAIJInfo{};
+  info->format = f.format;
+  if (f.format == 1) {
+    info->B = 1;
+    info->nd = f.dia.nd;
+    info->ncls = f.dia.ncls;
+    info->lds_bytes = (int64_t)cfp::dia_lds_bytes(sizeof(VS), f.dia.ncls, f.dia.nd);
+  } else if (f.format == 2) {
+    info->B = f.bdia.B;
+    info->nd = f.bdia.nd;
+    info->ncls = f.bdia.ncls;
+    info->nblk = f.bdia.nblk;
+    info->re = f.bdia.re;
+    info->lds_bytes = (int64_t)cfp::bdia_lds_bytes(sizeof(VS), f.bdia.B, (size_t)f.bdia.nblk);
   }
   return PETSC_SUCCESS;
 }

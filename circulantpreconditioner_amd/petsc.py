@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._lib import CirculantError, lib
-from ._lib_ext import FFTPrecTransportContext, PetscScalar, StructuredTransportContext
+from ._lib_ext import AIJInfo, FFTPrecTransportContext, PetscScalar, StructuredTransportContext
 
 PETSC_COMM_WORLD = 0
 PETSC_COMM_SELF = 1
@@ -397,6 +397,13 @@ class Mat:
         f = ctypes.c_int()
         PetscCall(lib().PetscMiniMatAIJGetFormat(self.h, ctypes.byref(f)))
         return {1: "dia", 2: "bdia", 0: "csr"}.get(f.value, "none")
+
+    def aij_info(self) -> dict:
+        """PetscMiniMatAIJDescribe: the form the next device MatMult will use, chosen on the host
+        (no device needed): format 'csr' / 'dia' / 'bdia', B, nd, ncls, nblk, re, lds_bytes."""
+        info = AIJInfo()
+        PetscCall(lib().PetscMiniMatAIJDescribe(self.h, ctypes.byref(info)))
+        return info.as_dict()
 
     def shift(self, a) -> "Mat":
         PetscCall(lib().MatShift(self.h, _S(a)))

@@ -20,6 +20,7 @@ import threading
 import numpy as np
 
 from ._lib import CirculantError
+from ._lib_ext import AIJInfo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libcirculant_fft_real.so")
@@ -28,7 +29,7 @@ _lib = None
 
 PETSC_COMM_WORLD, PETSC_COMM_SELF = 0, 1
 INSERT_VALUES, ADD_VALUES = 1, 2
-NORM_2 = 1
+NORM_1, NORM_2, NORM_INFINITY = 0, 1, 3
 MATOP_MULT = 0
 
 
@@ -75,6 +76,17 @@ def _declare(L) -> None:
         "VecNorm": ([vp, c_int, P(d)], c_int),
         "VecDot": ([vp, vp, P(d)], c_int),
         "VecAXPY": ([vp, d, vp], c_int),
+        "VecAYPX": ([vp, d, vp], c_int),
+        "VecWAXPY": ([vp, d, vp, vp], c_int),
+        "VecShift": ([vp, d], c_int),
+        "VecPointwiseMult": ([vp, vp, vp], c_int),
+        "VecPointwiseDivide": ([vp, vp, vp], c_int),
+        "VecMDot": ([vp, i64, P(vp), P(d)], c_int),
+        "VecMAXPY": ([vp, i64, P(d), P(vp)], c_int),
+        "VecMiniMAXPYNorm": ([vp, i64, P(d), P(vp), c_int, P(d)], c_int),
+        "VecMiniMDotMAXPYNorm": ([vp, i64, P(d), P(vp), P(d), P(d)], c_int),
+        "PetscMiniMatAIJGetFormat": ([vp, P(c_int)], c_int),
+        "PetscMiniMatAIJDescribe": ([vp, P(AIJInfo)], c_int),
         "MatCreateFFT": ([c_int, i64, P(i64), ctypes.c_char_p, P(vp)], c_int),
         "MatCreateVecsFFTW": ([vp, P(vp), P(vp), P(vp)], c_int),
         "MatCreateSeqAIJWithArrays": ([c_int, i64, i64, P(i64), P(i64), P(d), P(vp)], c_int),
@@ -298,6 +310,35 @@ def mat_aij(A_csr) -> ctypes.c_void_p:
                                               jp.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                               v.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(M)))
     return M
+
+
+def mat_aij_info(M) -> dict:
+    """PetscMiniMatAIJDescribe (petsc.Mat.aij_info): the form the next device MatMult will use,
+    chosen on the host; no device needed."""
+    info = AIJInfo()
+    PetscCall(lib().PetscMiniMatAIJDescribe(M, ctypes.byref(info)))
+    return info.as_dict()
+
+
+def mat_aij_format(M) -> str:
+    """PetscMiniMatAIJGetFormat: 'dia', 'bdia', 'csr', or 'none' before the first device MatMult."""
+    f = ctypes.c_int()
+    PetscCall(lib().PetscMiniMatAIJGetFormat(M, ctypes.byref(f)))
+    return {1: "dia", 2: "bdia", 0: "csr"}.get(f.value, "none")
+
+
+def mat_mult(M, x: Vec, y: Vec) -> Vec:
+    PetscCall(lib().MatMult(M, x.h, y.h))
+    return y
+
+
+def mat_shift(M, a: float) -> None:
+    PetscCall(lib().MatShift(M, float(a)))
+
+
+def mat_destroy(M) -> None:
+    if M is not None and M.value:
+        PetscCall(lib().MatDestroy(ctypes.byref(M)))
 
 
 def pc_shell(ctx: FFTPrecTransportContext) -> ctypes.c_void_p:

@@ -166,10 +166,21 @@ PetscErrorCode PetscMiniCommResolve(MPI_Comm comm, MPI_Comm *resolved);
 PetscErrorCode PetscMiniAllreduce(MPI_Comm comm, double *buf, int64_t count, int op);
 /* Device storage the stand-in AIJ picked at its first device MatMult: 1 = row-class diagonal
  * form (k_dia_spmv: nonzeros on <= 8 fixed diagonals, <= 256 distinct rows -- Cartesian
- * stencils), 2 = block row-class form (k_bdia_spmv: B x B blocks, B = 2..4, on <= 8 block
- * diagonals, <= 256 distinct block rows -- the interleaved wave operator), 0 = CSR, -1 = not
- * uploaded yet (MatShift resets it). */
+ * stencils), 2 = block row-class form (k_bdia_spmv: B x B blocks, B = 2..4, on <= 16 block
+ * diagonals, <= 256 distinct block rows, the table within the launch's LDS limit -- the
+ * interleaved wave operator), 0 = CSR, -1 = not uploaded yet (MatShift resets it). */
 PetscErrorCode PetscMiniMatAIJGetFormat(Mat A, int *format);
+/* The form the next device MatMult of an AIJ will use, chosen from the host CSR by the same
+ * builders as the upload: no device memory is touched and no HIP device is needed.  format as
+ * above (0 / 1 / 2); B = block size (1 for the row-class form), nd = diagonals, ncls = classes,
+ * nblk = blocks in the class table and re = 1 when the table is real-valued (block form only);
+ * lds_bytes = the dynamic LDS the launch requests (0 for CSR).  A MATMPIAIJ describes its
+ * diagonal block. */
+typedef struct {
+  int format, B, nd, ncls, nblk, re;
+  int64_t lds_bytes;
+} PetscMiniAIJInfo;
+PetscErrorCode PetscMiniMatAIJDescribe(Mat A, PetscMiniAIJInfo *info);
 /* The device row-class form of an AIJ (above; uploaded now if it has not been): its class bytes,
  * class masks and coefficient table as device arrays, in the layout of cfp_stencil_t
  * (include/circulant_fft.h).  *has = PETSC_FALSE when the matrix is not representable (CSR only).
