@@ -15,7 +15,9 @@
 //       256-point z DFT, divide by the separable symbol at (kx, k1 + N1 k2, kz), then the same
 //       transforms on the conjugate (inverse)
 //       (k_tp_mid_rec, 256^3 default shape, a transport symbol with |a| <= 1 - 2^-13: the same
-//       array without the z transforms, z solved as the recurrence u_z = a u_{z-1} + w_z)
+//       array and the same 8 rows x 128 B accesses (lane = x + 8 y2) without the z transforms:
+//       y2 DFT across lane bits 3..5, z solved as the recurrence u_z = a u_{z-1} + w_z in the
+//       registers of the lane that owns the column, one carry per wave)
 //   P3  k_tp_rows<inv>: P1 on the conjugate, x 1/N
 //
 // P1/P3 workgroups are N1 x 16 threads x 16 points with a split-LDS exchange buffer of
@@ -915,23 +917,28 @@ k_tp_mid_sw(cd* data, TPArgs a, int nunits) {
 // The host enables it only where max |a| <= 1 - 2^-13 (cfp_plan.hip); k_tp_mid_sw's output is the
 // same array, so P1 and P3 do not change.
 //
-// The tile is k_tp_mid_sw's (8 x times 8 y2 times 256 z, 128-byte runs, in place).  A thread
-// holds 8 y2 times 2 consecutive z, a wave 8 x times 16 z (lane = x + 8 zl, z = 16 wave + 2 zl + j,
-// slot m = 8 j + y2): the y2 DFT is a register radix-8 and the scan runs thread -> lane bits
-// 3..5 -> waves.  Lane levels: a hypercube scan on xor exchanges (DPP row_ror:8, permlane16 /
-// permlane32 swaps), each level merging (block total S, exclusive prefix X) of two blocks of
-// 2, 4, 8 z with a^2, a^4, a^8.  Wave level: every wave writes its 64 columns' block-end values
-// E_w (16 KiB), one workgroup barrier, then lane (x, zl) forms the carry into its wave for
-// column (x, k2 = zl),
+// The tile is k_tp_mid_sw's (8 x times 8 y2 times 256 z, 128-byte runs, in place), and so is the
+// access: lane = x + 8 y2, so one wave-wide load or store is the 8 rows times 128 bytes of one
+// z-plane (4 KiB apart).  A wave holds 16 consecutive z (z = 16 wave + m, slot m), a thread the
+// 16 z of one (x, y2).  The y2 DFT runs across lane bits 5, 4, 3 on all 16 slots: radix-2 DIF,
+// natural order in, bit-reversed out.  Bits 5 and 4: a permlane32 / permlane16 swap of a slot
+// pair gives each lane of a lane pair one slot's two inputs, the lane runs that butterfly whole,
+// and a second swap returns the results to their owners; bit 3: DPP row_ror:8 and one fma with a
+// per-lane sign; stage twiddles are per-lane constants.  Lane (x, y2) then owns column
+// (x, k2 = brev3(y2)) and the scan is a register loop: t_m = a t_{m-1} + r v_m over the 16
+// slots.  Wave level: every wave writes its 64 columns' block-end values E_w = t_15 (16 KiB),
+// one workgroup barrier, then each lane forms the carry into its wave for its own column,
 //   U_{16 w - 1} = sum_k a^{16 k} E_{(w - 1 - k) mod 16} / (1 - a^256)   (Horner in a^16),
-// and the 8 lanes of an x exchange their columns' carries (ds_bpermute).  That barrier is the
-// only one of a unit; the block-end buffer alternates between two units, so a wave that runs
-// ahead writes the next unit's values while others still read this one's.
+// and adds a^{m+1} U to slot m (a running product).  That barrier is the only one of a unit; the
+// block-end buffer alternates between two units, so a wave that runs ahead writes the next
+// unit's values while others still read this one's.  The inverse y2 DFT is the forward DIT on the
+// conjugate, from the bit-reversed order back to natural over lane bits 3, 4, 5.
 //
-// The columns' a and r = 256 / (c + lamz) come from a table that wave 0 fills one unit ahead.
+// The columns' a and r = 256 / (c + lamz) come from a table that wave 0 fills one unit ahead
+// (lane (x, y2) fills column (x, brev3(y2)), the column that lane scans).
 //
-// PF: slots 0..6 of the next unit come by LDS-DMA into this wave's own 7 KiB, issued as
-// soon as the wave has this unit's values in registers, so they fly for nearly a whole unit; a buffer
+// PF: slots 0..6 of the next unit come by LDS-DMA into this wave's own 7 KiB, issued between
+// the unit's last arithmetic and its stores (measured best there, see the unit's end); a buffer
 // that is only 8-byte aligned runs without it (global_load_lds_dwordx4 takes 16-byte addresses).
 //
 // The body is a function of __restrict__ pointers to the kernel's LDS arrays: inlined, its LDS
@@ -945,7 +952,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
   constexpr int TN = 256, N2 = 8, N1 = TN / N2, XT = 8, NXT = TN / XT, NW = 16;
   constexpr int NPF = PF ? kRecNPF : 0;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, x = lane & 7, zl = lane >> 3;
+  const int lane = tid & 63, x = lane & 7, y2 = lane >> 3;
   const int wv = __builtin_amdgcn_readfirstlane(tid / 64);
   const i64 zs = (i64)TN << (a.lnyl ? a.lnyl : ilog2(TN));
   const cd lz = a.lamz;
@@ -955,13 +962,14 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
     asm volatile("" : "+v"(i));
     return i;
   };
-  // Column table of unit u: lane c = x + 8 k2 of wave 0 loads the symbol of column (x, k2) and
+  // Column table of unit u: lane c = x + 8 y2 of wave 0 loads the symbol of column (x, brev3(y2)),
+  // the column every wave's lane c scans after the y2 DFT, and
   // writes a = lamz / (c + lamz) and r = 256 / (c + lamz), one unit ahead (the unit's barrier
   // publishes it; three buffers: waves behind that barrier still read the previous unit's).
   // One division per column and unit instead of one per thread, and no global load inside the
   // unit, whose wait would also wait for the prefetch in flight.
   const auto colsym_of = [&](int u) {
-    return a.colsym[(u % NXT) * XT + x + (i64)TN * (a.k1_off + u / NXT + N1 * zl)];
+    return a.colsym[(u % NXT) * XT + x + (i64)TN * (a.k1_off + u / NXT + N1 * brev<N2>(y2))];
   };
   const auto ctab_put = [&](int buf, cd cs) {
     const cd den = make_cd(cs.x + 1.0 + lz.x, cs.y + lz.y);
@@ -973,12 +981,12 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
   if (tid < TN) tw_l[tid] = a.tw[tid];
   if (wv == 0 && (int)blockIdx.x < nunits) ctab_put(0, colsym_of((int)blockIdx.x));
   __syncthreads();
-  // a point's address = a wave-uniform base (unit u = (x tile, local k1): row 8 k1, z = 16 wv;
-  // slot m: row + (m & 7), z + (m >> 3)) + this lane's 32-bit byte offset (x, z = 2 zl): a scalar
-  // base plus one offset register for all 16 slots, instead of 16 address pairs
-  const unsigned loff = 16u * ((unsigned)x + (unsigned)zs * 2u * (unsigned)zl);
+  // a point's address = a wave-uniform base (unit u = (x tile, local k1): row 8 k1; slot m:
+  // z = 16 wv + m) + this lane's 32-bit byte offset (x, row y2): a scalar base plus one offset
+  // register for all 16 slots, instead of 16 address pairs
+  const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);
   const auto slot_ptr = [&](int u, int m) {
-    return data + ((u % NXT) * XT + (i64)TN * (N2 * (u / NXT) + (m & 7)) + zs * (16 * wv + (m >> 3)));
+    return data + ((u % NXT) * XT + (i64)TN * N2 * (u / NXT) + zs * (16 * wv + m));
   };
   const auto at = [](cd* base, unsigned off) { return reinterpret_cast<cd*>(reinterpret_cast<char*>(base) + off); };
   const auto prefetch = [&](int u) {  // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
@@ -992,8 +1000,35 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
   if constexpr (PF) {
     if ((int)blockIdx.x < nunits) prefetch((int)blockIdx.x);
   }
-  const bool up3 = (zl & 1) != 0, up4 = (zl & 2) != 0, up5 = (zl & 4) != 0;
-  const cd zero = make_cd(0.0, 0.0), one = make_cd(1.0, 0.0);
+  const cd zero = make_cd(0.0, 0.0);
+  // The y2 DFT's per-lane constants: the sign of the DPP stage (+1 where lane bit 3 is clear, -1
+  // where set) and the stage twiddles W_8^{y2 & 3} (lane bit 5) and W_4^{y2 & 1} (lane bit 4),
+  // which the two lanes of a pair share.
+  const double s3 = (y2 & 1) ? -1.0 : 1.0;
+  const cd w8 = a.tw[(TN / 8) * (y2 & 3)], w4 = a.tw[(TN / 4) * (y2 & 1)];
+  // Radix-2 stage over lane bit B (5 or 4) on the slot pair (p, q): the swap gives the lower lane
+  // both lanes' p and the upper lane both lanes' q, each lane runs one whole butterfly (no
+  // duplicated value, no half thrown away), and the second swap hands every lane its own results
+  // back: sums to the lower lane, differences to the upper.  DIF: a + b, (a - b) w.
+  const auto dif2 = [](auto bit, cd& p, cd& q, cd w) {
+    constexpr int B = decltype(bit)::value;
+    swap_c<B>(p, q);
+    const cd s = cadd(p, q), d = cmul(csub(p, q), w);
+    p = s;
+    q = d;
+    swap_c<B>(p, q);
+  };
+  // DIT: a + b w, a - b w
+  const auto dit2 = [](auto bit, cd& p, cd& q, cd w) {
+    constexpr int B = decltype(bit)::value;
+    swap_c<B>(p, q);
+    const cd t = cmul(q, w);
+    q = csub(p, t);
+    p = cadd(p, t);
+    swap_c<B>(p, q);
+  };
+  using bit5 = std::integral_constant<int, 5>;
+  using bit4 = std::integral_constant<int, 4>;
   // pin(): the values are formed where the source forms them.  Sunk towards their uses, a DFT's
   // or a column's last operations keep their inputs live as well and the kernel goes to scratch.
   const auto pin = [](cd& w) { asm volatile("" : "+v"(w.x), "+v"(w.y)); };
@@ -1033,95 +1068,44 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
       }
     }
     if (more && wv == 0) ctab_put(nbuf, csn);
-    // twiddle W_256^{y2 k1} (uniform over the workgroup), then the y2 DFT: natural order in and out
+    // twiddle W_256^{y2 k1}: one per thread (k1 uniform over the workgroup, y2 the lane's)
+    {
+      const cd w = tw_l[((idx(lane) >> 3) * k1) & (TN - 1)];
 #pragma unroll
-    for (int y = 1; y < N2; ++y) {
-      const cd w = tw_l[(y * k1) & (TN - 1)];
-      v[y] = cmul(v[y], w);
-      v[8 + y] = cmul(v[8 + y], w);
+      for (int m = 0; m < 16; ++m) v[m] = cmul(v[m], w);
     }
-    // The next unit's prefetch, once every load of this one has landed (pin: the values are in
-    // their registers, so the prefetch buffer is free as well).  While an LDS-DMA is in flight
-    // the compiler turns every wait for a global load into vmcnt(0), the DMA included: issued
-    // before the loads are consumed it would be drained at their first use.  From here it flies
-    // until the next unit's top.
-    if constexpr (PF && more && !(PROBE & PR_NO_LOAD)) {
-#pragma unroll
-      for (int m = 0; m < 16; ++m) pin(v[m]);
-      prefetch(it + (int)gridDim.x);
-    }
-    // (the scheduling barriers keep one DFT's, one column's, one level's temporaries live at a time)
+    // (the scheduling barriers keep a few slots' temporaries live at a time)
     __builtin_amdgcn_sched_barrier(0);
+    // y2 DFT across lane bits 5, 4, 3 (DIF): lane (x, y2) ends as frequency k2 = brev3(y2)
     if constexpr (!(PROBE & PR_NO_Y2)) {
-      dft_reg<8>(v);
 #pragma unroll
-      for (int m = 0; m < 8; ++m) pin(v[m]);
-      __builtin_amdgcn_sched_barrier(0);
-      dft_reg<8>(v + 8);
-#pragma unroll
-      for (int m = 8; m < 16; ++m) pin(v[m]);
-      __builtin_amdgcn_sched_barrier(0);
+      for (int m = 0; m < 16; m += 2) {
+        dif2(bit5{}, v[m], v[m + 1], w8);
+        dif2(bit4{}, v[m], v[m + 1], w4);
+        v[m] = bfly_l3(v[m], s3);
+        v[m + 1] = bfly_l3(v[m + 1], s3);
+        pin(v[m]);
+        pin(v[m + 1]);
+        if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
+      }
     }
     if constexpr (!(PROBE & PR_NO_ZMATH)) {
-      const auto pow2zl = [&](cd aa) {  // a^{2 zl}
-        cd pw = cmul(aa, aa), q = up3 ? pw : one;
-        pw = cmul(pw, pw);
-        q = up4 ? cmul(q, pw) : q;
-        pw = cmul(pw, pw);
-        return up5 ? cmul(q, pw) : q;
-      };
+      const int ln = idx(lane);
+      const cd aa = ctab[(2 * buf) * 64 + ln];  // this lane's column (x, k2)
+      // the wave-local solution (zero carry into the wave) without its factor r:
+      // s_m = a s_{m-1} + v_m, t_m = r s_m (r joins in the fix-up's multiply-add below)
 #pragma unroll
-      for (int k2 = 0; k2 < 8; ++k2) {
-        const int c = (idx(lane) & 7) + 8 * k2;
-        const cd aa = ctab[(2 * buf) * 64 + c], r = ctab[(2 * buf + 1) * 64 + c];
-        const cd v0 = cmul(v[k2], r), v1 = cmul(v[8 + k2], r);
-        // thread total, then the lane levels: S = block total, X = value at the end of the
-        // previous thread (block-local, zero start); pw = a^2, a^4, a^8 and q = a^{2 (zl & 1)},
-        // a^{2 (zl & 3)}, each formed at its level
-        cd S = cfma(aa, v0, v1), X, lo, hi, pw = cmul(aa, aa), q;
-        __builtin_amdgcn_sched_barrier(0);
-        {
-          const cd pr = lane_xor8(S);
-          lo = up3 ? pr : S;
-          hi = up3 ? S : pr;
-          X = up3 ? lo : zero;
-          S = cfma(pw, lo, hi);
-          q = up3 ? pw : one;
-          pw = cmul(pw, pw);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        {
-          lo = S;
-          hi = S;
-          swap_c<4>(lo, hi);
-          if (up4) X = cfma(q, lo, X);
-          S = cfma(pw, lo, hi);
-          q = up4 ? cmul(q, pw) : q;
-          pw = cmul(pw, pw);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        {
-          lo = S;
-          hi = S;
-          swap_c<5>(lo, hi);
-          if (up5) X = cfma(q, lo, X);
-          S = cfma(pw, lo, hi);  // the wave's block-end value, in every lane
-        }
-        v[k2] = cfma(aa, X, v0);  // the wave-local solution (zero carry into the wave)
-        v[8 + k2] = cfma(aa, v[k2], v1);
-        pin(v[k2]);
-        pin(v[8 + k2]);
-        if (zl == k2) carr[(par * NW + wv) * 64 + idx(lane)] = S;
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      for (int m = 1; m < 16; ++m) v[m] = cfma(aa, v[m - 1], v[m]);
+      const cd E = cmul(ctab[(2 * buf + 1) * 64 + ln], v[15]);
+      carr[(par * NW + wv) * 64 + ln] = E;  // the wave's block-end value t_15 of this column
+#pragma unroll
+      for (int m = 0; m < 16; ++m) pin(v[m]);
       lds_barrier();  // the unit's only barrier: every wave's block-end values are in carr[par]
-      cd cin;  // the carry into this wave for column (x, k2 = zl)
+      cd cin;  // the carry into this wave for this lane's column
       {
-        const int ln = idx(lane);
-        const cd am = ctab[(2 * buf) * 64 + ln];
-        const cd am2 = cmul(am, am), am4 = cmul(am2, am2), am8 = cmul(am4, am4);
+        const cd am2 = cmul(aa, aa), am4 = cmul(am2, am2), am8 = cmul(am4, am4);
         const cd A = cmul(am8, am8);  // a^16
-        cd acc = carr[(par * NW + wv) * 64 + ln];
+        cd acc = E;                   // E_wv
 #pragma unroll
         for (int k = 14; k >= 0; --k) {
           acc = cfma(acc, A, carr[(par * NW + ((wv - 1 - k) & 15)) * 64 + ln]);
@@ -1132,57 +1116,57 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
         const double id = 1.0 / fma(d.x, d.x, d.y * d.y);
         cin = make_cd(fma(acc.x, d.x, acc.y * d.y) * id, fma(acc.y, d.x, -acc.x * d.y) * id);
       }
+      // u_m = r s_m + a^{m+1} cin
+      const cd r = ctab[(2 * buf + 1) * 64 + ln];
+      cd g = cmul(aa, cin);
 #pragma unroll
-      for (int k2 = 0; k2 < 8; ++k2) {
-        const int c = (idx(lane) & 7) + 8 * k2;
-        const long long bx = __double_as_longlong(cin.x), by = __double_as_longlong(cin.y);
-        const unsigned xl = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(bx & 0xffffffffll));
-        const unsigned xh = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(bx >> 32));
-        const unsigned yl = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(by & 0xffffffffll));
-        const unsigned yh = (unsigned)__builtin_amdgcn_ds_bpermute(4 * c, (int)(by >> 32));
-        const cd ci = make_cd(__longlong_as_double((long long)(((unsigned long long)xh << 32) | xl)),
-                              __longlong_as_double((long long)(((unsigned long long)yh << 32) | yl)));
-        // weights a^{2 zl + 1}, a^{2 zl + 2} of the carry at this thread's two z, rebuilt from
-        // the column's a (kept across the barrier they cost 64 VGPRs)
-        const cd aa = ctab[(2 * buf) * 64 + c];
-        const cd g = cmul(cmul(aa, pow2zl(aa)), ci);
-        v[k2] = cadd(v[k2], g);
-        v[8 + k2] = cfma(aa, g, v[8 + k2]);
-        pin(v[k2]);
-        pin(v[8 + k2]);
-        __builtin_amdgcn_sched_barrier(0);
+      for (int m = 0; m < 16; ++m) {
+        v[m] = cfma(r, v[m], g);
+        if (m < 15) g = cmul(aa, g);
       }
     }
-    // inverse y2 DFT on the conjugate, conjugate twiddle, store
-#pragma unroll
-    for (int m = 0; m < 16; ++m) v[m] = cconj(v[m]);
-    if constexpr (!(PROBE & PR_NO_Y2)) {
-      dft_reg<8>(v);
-#pragma unroll
-      for (int m = 0; m < 8; ++m) pin(v[m]);
-      __builtin_amdgcn_sched_barrier(0);
-      dft_reg<8>(v + 8);
-#pragma unroll
-      for (int m = 8; m < 16; ++m) pin(v[m]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    // inverse y2 DFT on the conjugate (DIT over lane bits 3, 4, 5: bit-reversed in, natural
+    // out), conjugate twiddle, then the next unit's prefetch and this unit's stores
     {
-      // opaque copies: the twiddles are read again and the addresses formed again, instead of
+      // opaque copies: the twiddle is read again and the addresses formed again, instead of
       // living in registers since the loads
       int k1s = k1, us = u;
       unsigned lo2 = loff;
       asm volatile("" : "+s"(k1s), "+s"(us), "+v"(lo2));
+      const cd w = tw_l[((idx(lane) >> 3) * k1s) & (TN - 1)];
+#pragma unroll
+      for (int m = 0; m < 16; m += 2) {
+        cd p = cconj(v[m]), q = cconj(v[m + 1]);
+        if constexpr (!(PROBE & PR_NO_Y2)) {
+          p = bfly_l3(p, s3);
+          q = bfly_l3(q, s3);
+          dit2(bit4{}, p, q, w4);
+          dit2(bit5{}, p, q, w8);
+        }
+        v[m] = cconj(cmul(p, w));
+        v[m + 1] = cconj(cmul(q, w));
+        pin(v[m]);
+        pin(v[m + 1]);
+        if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
+      }
+      // The next unit's prefetch goes out here, behind all of this unit's arithmetic and in
+      // front of its stores, which then leave in one burst.  Issued right after the loads (where
+      // it flies longest) and with the stores spread over the inverse DFT the same kernel takes
+      // 90.0 us instead of 86.0 (profiles/r08_zrows_probe.txt).  No global load follows it inside
+      // the unit, so no wait drains it early.
+      if constexpr (PF && more && !(PROBE & PR_NO_LOAD)) {
+        prefetch(it + (int)gridDim.x);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (!(PROBE & PR_NO_STORE)) {
+#pragma unroll
+        for (int m = 0; m < 16; ++m) gstore<0>(at(slot_ptr(us, m), lo2), v[m]);
+      }
       if constexpr (PROBE & PR_NO_STORE) {
         double acc = 0.0;
 #pragma unroll
         for (int m = 0; m < 16; ++m) acc += v[m].x + v[m].y;
         if (acc == 1.2345e300) *at(slot_ptr(us, 0), lo2) = make_cd(acc, 0.0);  // keeps the work live, never true
-      } else {
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-          const cd w = (m & 7) ? tw_l[((m & 7) * k1s) & (TN - 1)] : one;
-          gstore<0>(at(slot_ptr(us, m), lo2), cconj(cmul(v[m], w)));
-        }
       }
     }
     par ^= 1;
