@@ -216,6 +216,9 @@ def declare(L) -> None:
         "MatCreateFFTHIP": ([c_int, i64, P(i64), P(vp)], c_int),
         "MatFFTHIPGetPlan": ([vp, P(vp)], c_int),
         "MatFFTHIPGetSolveCounts": ([vp, P(i64), P(i64)], c_int),
+        "MatFFTHIPGetFusedBACount": ([vp, P(i64)], c_int),
+        "PCSetOperators": ([vp, vp, vp], c_int),
+        "applyFFT3DPrecTransportBA": ([vp, c_int, vp, vp, vp], c_int),
         "PetscObjectStateGet": ([vp, P(i64)], c_int),
         "PetscObjectGetId": ([vp, P(i64)], c_int),
         "MatCreateVecsFFTW": ([vp, P(vp), P(vp), P(vp)], c_int),

@@ -132,6 +132,12 @@ extern "C" PetscErrorCode MatFFTHIPGetSolveCounts(Mat A, PetscInt* own_symbol, P
   if (explicit_diag) *explicit_diag = s->solves_diag;
   return PETSC_SUCCESS;
 }
+extern "C" PetscErrorCode MatFFTHIPGetFusedBACount(Mat A, PetscInt* fused_ba) {
+  ShellBase* s;
+  PetscCall(shell_base(A, &s));
+  if (fused_ba) *fused_ba = s->fused_ba;
+  return PETSC_SUCCESS;
+}
 
 // ------------------------------------------------------------------ direct solver
 // build_transport_col, src/FftLinearSolver_3D.c:80-90

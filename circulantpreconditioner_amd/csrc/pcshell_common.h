@@ -222,6 +222,7 @@ struct CFP_INTERNAL ShellBase {
   PetscObjectState diag_state = 0;
   uint64_t diag_version = 0;
   PetscInt solves_own = 0, solves_diag = 0;  // solve_3D calls per path (MatFFTHIPGetSolveCounts)
+  PetscInt fused_ba = 0;                     // applyBA calls that took pc_fused_ba (MatFFTHIPGetFusedBACount)
 
   explicit ShellBase(int m) : magic(m) {}
   uint64_t symbol_version() const {

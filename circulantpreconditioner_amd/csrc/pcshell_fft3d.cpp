@@ -392,6 +392,7 @@ PetscErrorCode cfp_pc::pc_fused_ba(PC pc, FFTPrecTransportContext* ctx, Mat A, V
   PetscCall(shell_apply(s, y, x, true, nullptr, &ex));
   PetscCheck(ex.fused >= 0, PETSC_COMM_SELF, PETSC_ERR_PLIB, "applyFFT3DPrecTransportBA: fused apply not taken");
   if (req) req->done = PETSC_TRUE;
+  ++s->fused_ba;
   *taken = true;
 #endif
   return PETSC_SUCCESS;

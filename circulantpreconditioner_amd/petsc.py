@@ -382,6 +382,13 @@ class Mat:
         PetscCall(lib().MatFFTHIPGetSolveCounts(self.h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def fused_ba_count(self) -> int:
+        """MatFFTHIPGetFusedBACount: the applyFFT3DPrecTransportBA calls that formed A x inside the
+        apply's first sweep (the calls that ran MatMult and the apply separately do not count)."""
+        n = ctypes.c_int64()
+        PetscCall(lib().MatFFTHIPGetFusedBACount(self.h, ctypes.byref(n)))
+        return n.value
+
     def mult(self, x: Vec, y: Vec) -> Vec:
         PetscCall(lib().MatMult(self.h, x.h, y.h))
         return y
@@ -484,6 +491,10 @@ class PC:
     def apply(self, b: Vec, x: Vec) -> Vec:
         PetscCall(lib().PCApply(self.h, b.h, x.h))
         return x
+
+    def set_operators(self, A: "Mat", Pm: "Mat | None" = None) -> "PC":
+        PetscCall(lib().PCSetOperators(self.h, A.h, (Pm or A).h))
+        return self
 
     def destroy(self) -> None:
         if self.owned and self.h is not None and self.h.value:
@@ -629,6 +640,11 @@ def context_remap_back(ctx: FFTPrecTransportContext) -> int:
 
 def applyFFT3DPrecTransport(pc: PC, b: Vec, x: Vec) -> None:
     PetscCall(lib().applyFFT3DPrecTransport(pc.h, b.h, x.h))
+
+
+def applyFFT3DPrecTransportBA(pc: PC, side: int, x: Vec, y: Vec, work: Vec) -> None:
+    """The PCShellSetApplyBA callback: y = B A x (PC_LEFT) or A B x (PC_RIGHT), A the PC's operator."""
+    PetscCall(lib().applyFFT3DPrecTransportBA(pc.h, int(side), x.h, y.h, work.h))
 
 
 def setupFFTPrec3D(pc: PC) -> None:

@@ -122,6 +122,9 @@ PetscErrorCode MatFFTHIPGetDistPlan(Mat A, struct cfp_dist_plan_s **plan);
  * (Diag untouched since setupFFTPrec3D materialised it: same object id and PetscObjectState,
  * symbol unchanged) and how many streamed the Diag they were given. */
 PetscErrorCode MatFFTHIPGetSolveCounts(Mat A, PetscInt *own_symbol, PetscInt *explicit_diag);
+/* How many applyFFT3DPrecTransportBA calls on this FFT matrix formed A x inside the apply's first
+ * sweep (the fused route); the calls that ran MatMult and the apply separately do not count. */
+PetscErrorCode MatFFTHIPGetFusedBACount(Mat A, PetscInt *fused_ba);
 /* Side table of this build's per-context additions (not in the struct, see above).
  * remapBack: Cartesian -> mesh remap applied to the solve's result (NULL, the default: x stays
  * on the Cartesian grid, as the reference's apply leaves it).  The Mat stays the caller's.
