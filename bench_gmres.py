@@ -16,6 +16,7 @@ calls and the host wall time spent inside them.
     python bench_gmres.py                          # configs 1, 3 and 4
     python bench_gmres.py --system transport --grid 128 --sign fixed --pc fft --steps 5
     python bench_gmres.py --system wave --wave-grid 64 --wave-steps 3
+    python bench_gmres.py --system diffusion --diffusion-grid 256   # advection-diffusion, PCNONE and the diffusion PCSHELL
 """
 from __future__ import annotations
 
@@ -27,7 +28,9 @@ import time
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--system", nargs="*", default=["transport", "wave"], choices=["transport", "wave", "wave2d", "mesh", "direct"])
+    ap.add_argument("--system", nargs="*", default=["transport", "wave"], choices=["transport", "wave", "wave2d", "mesh", "direct", "diffusion"])
+    ap.add_argument("--diffusion-grid", type=int, nargs="*", default=[32, 256],
+                    help="--system diffusion: the implicit advection-diffusion step (walls, nu = 0.01, dt = 0.01)")
     ap.add_argument("--direct-grid", type=int, nargs="*", default=[10, 100, 256],
                     help="--system direct: the direct-solver loop (TransportEquationFFT_impl) on n^3")
     ap.add_argument("--mesh", nargs="*", default=["mesh_tetra_1.msh", "3DKershawTetra1.msh", "mesh_hexa_3.msh"],
@@ -64,6 +67,8 @@ def main(argv=None) -> int:
         lines += mesh_lines(args)
     if "direct" in args.system:
         lines += direct_lines(args)
+    if "diffusion" in args.system:
+        lines += diffusion_lines(args)
     for n in (args.grid if "transport" in args.system else []):
         for sign in args.sign:
             for pc in args.pc:
@@ -116,6 +121,32 @@ def direct_lines(args) -> list:
                     "grid": n, "run": label, "steps": r["steps"], "dt": r["dt"], "lambda": r["lambda"],
                     "ms_per_step": 1e3 * r["solve_seconds"] / max(1, r["steps"]),
                     "solves_per_s": r["steps"] / r["solve_seconds"] if r["solve_seconds"] > 0 else None,
+                    "setup_s": r["setup_seconds"], "wall_s": wall}
+            print(json.dumps(line), flush=True)
+            out.append(line)
+    return out
+
+
+def diffusion_lines(args) -> list:
+    """The implicit advection-diffusion step (include/diffusion_equation.h) on n^3 with walls: GMRES with
+    PCNONE and with the diffusion PCSHELL (at 256^3 its middle sweep is the two-sided z recurrence)."""
+    from circulantpreconditioner_amd import diffusion as D
+    out = []
+    for n in args.diffusion_grid:
+        for pc in args.pc:
+            kw = dict(pc=pc, bc="wall", device=True, max_its=args.max_its, precision=1e-5, steps=args.steps or 1)
+            t0 = time.perf_counter()
+            r = D.run(D.config(n, **kw))
+            wall = time.perf_counter() - t0
+            its = max(1, r["total_its"])
+            line = {"metric": "GMRES advection-diffusion step",
+                    "config": f"{n}^3 advection-diffusion (walls), GMRES(30), 1 MI355X", "grid": n, "pc": pc,
+                    "steps": r["steps"], "dt": r["dt"], "lambda": r["lambda"], "mu": r["mu"],
+                    "gmres_its": r["total_its"], "its_per_step": [r["min_step_its"], r["max_step_its"]],
+                    "converged": bool(r["all_converged"]), "last_residual": r["last_residual"],
+                    "ms_per_solve": 1e3 * r["solve_seconds"] / max(1, r["steps"]),
+                    "ms_per_iteration": 1e3 * r["solve_seconds"] / its, "pc_calls": r["pc_calls"],
+                    "pc_ms_per_call": 1e3 * r["pc_seconds"] / max(1, r["pc_calls"]),
                     "setup_s": r["setup_seconds"], "wall_s": wall}
             print(json.dumps(line), flush=True)
             out.append(line)

@@ -66,6 +66,50 @@ class TransportResult(ctypes.Structure):
         return d
 
 
+class FFTPrecDiffusionContext(ctypes.Structure):
+    """struct FFTPrecDiffusionContext (include/diffusion_equation.h): the transport context's 12
+    members in order, then mu_x, mu_y, mu_z."""
+    _fields_ = FFTPrecTransportContext._fields_ + [("mu_x", PetscScalar), ("mu_y", PetscScalar), ("mu_z", PetscScalar)]
+
+
+class StructuredDiffusionContext(ctypes.Structure):
+    """struct StructuredDiffusionContext (include/diffusion_equation.h), passed by value."""
+    _fields_ = [("n_x", ctypes.c_int64), ("n_y", ctypes.c_int64), ("n_z", ctypes.c_int64),
+                ("a_x", PetscScalar), ("a_y", PetscScalar), ("a_z", PetscScalar), ("nu", PetscScalar),
+                ("dt", PetscScalar), ("delta_x", PetscScalar), ("delta_y", PetscScalar), ("delta_z", PetscScalar),
+                ("FFT_MAT", ctypes.c_void_p)]
+
+
+class AdvDiffConfig(ctypes.Structure):
+    """cfp_advdiff_config (include/diffusion_equation.h)."""
+    _fields_ = [("nx", ctypes.c_int64), ("ny", ctypes.c_int64), ("nz", ctypes.c_int64),
+                ("xmin", ctypes.c_double * 3), ("xmax", ctypes.c_double * 3), ("a", ctypes.c_double * 3),
+                ("nu", ctypes.c_double), ("dt", ctypes.c_double), ("tmax", ctypes.c_double), ("ntmax", ctypes.c_int64),
+                ("precision", ctypes.c_double), ("max_its", ctypes.c_int64), ("restart", ctypes.c_int64),
+                ("pc", ctypes.c_int), ("bc", ctypes.c_int), ("pc_side", ctypes.c_int), ("on_device", ctypes.c_int),
+                ("profile", ctypes.c_int)]
+
+
+class AdvDiffResult(ctypes.Structure):
+    """cfp_advdiff_result (include/diffusion_equation.h)."""
+    _fields_ = [("steps", ctypes.c_int64), ("dt", ctypes.c_double), ("time", ctypes.c_double),
+                ("total_its", ctypes.c_int64), ("max_step_its", ctypes.c_int64), ("min_step_its", ctypes.c_int64),
+                ("last_reason", ctypes.c_int), ("all_converged", ctypes.c_int), ("last_residual", ctypes.c_double),
+                ("last_norm_dU", ctypes.c_double), ("solve_seconds", ctypes.c_double),
+                ("pc_seconds", ctypes.c_double), ("pc_calls", ctypes.c_int64), ("setup_seconds", ctypes.c_double),
+                ("lambda_", ctypes.c_double * 3), ("mu_", ctypes.c_double * 3), ("loop_seconds", ctypes.c_double),
+                ("dev_ms_", ctypes.c_double * 4), ("dev_launches_", ctypes.c_int64 * 4),
+                ("fused_dots", ctypes.c_int64), ("fused_norms", ctypes.c_int64)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_")}
+        d["lambda"] = list(self.lambda_)
+        d["mu"] = list(self.mu_)
+        d["dev_ms"] = dict(zip(("pcapply", "matmult", "vector", "copy"), self.dev_ms_))
+        d["dev_launches"] = dict(zip(("pcapply", "matmult", "vector", "copy"), self.dev_launches_))
+        return d
+
+
 class AIJInfo(ctypes.Structure):
     """PetscMiniAIJInfo (include/petsc_mini.h): the device form an AIJ's MatMult will use."""
     _fields_ = [("format", ctypes.c_int), ("B", ctypes.c_int), ("nd", ctypes.c_int), ("ncls", ctypes.c_int),
@@ -111,6 +155,9 @@ def declare(L) -> None:
     S, P, cs = PetscScalar, ctypes.POINTER, ctypes.c_char_p
     sig = {
         "cfp_plan_mid_kernel": ([vp, P(c_int)], c_int), "cfp_transport_z_ratio": ([i64, i64, dp, P(ctypes.c_double)], c_int),
+        "cfp_plan_set_symbol_advdiff": ([vp, dp, dp], c_int),
+        "cfp_advdiff_symbol_1d": ([i64, P(ctypes.c_double), P(ctypes.c_double), dp], c_int),
+        "cfp_advdiff_z_ratio": ([i64, i64, dp, dp, P(ctypes.c_double)], c_int),
         # slab-distributed plan over RCCL + single-process group
         "cfp_dist_get_unique_id": ([ctypes.c_char_p], c_int),
         "cfp_dist_unique_id_bytes": ([], c_int),
@@ -275,6 +322,20 @@ def declare(L) -> None:
         "cfp_transport_config_default": ([P(TransportConfig), i64], None),
         "TransportEquationGMRES": ([P(TransportConfig), P(TransportResult), P(ctypes.c_double)], c_int),
         "TransportEquationFFTDirect": ([P(TransportConfig), P(TransportResult), P(ctypes.c_double)], c_int),
+        # advection-diffusion: PCSHELL, direct solver, operator, time loops (include/diffusion_equation.h)
+        "getFFTPrec3DDiffusionContext": ([i64, S, i64, i64, i64, S, S, S, S, P(ctypes.c_double), P(ctypes.c_double),
+                                          P(FFTPrecDiffusionContext)], c_int),
+        "setupFFTPrec3DDiffusion": ([vp], c_int),
+        "applyFFT3DPrecDiffusion": ([vp, vp, vp], c_int),
+        "destroyFFTPrec3DDiffusion": ([vp], c_int),
+        "PetscFft3DDiffusionSolver": ([StructuredDiffusionContext, vp, vp], c_int),
+        "cfp_advdiff_csr": ([i64, i64, i64, P(ctypes.c_double), ctypes.c_double, P(ctypes.c_double), ctypes.c_double,
+                             c_int, ctypes.c_double, P(i64), P(i64), P(ctypes.c_double), P(i64)], c_int),
+        "computeAdvectionDiffusionMatrixCartesianAIJ": ([c_int, i64, i64, i64, P(ctypes.c_double), ctypes.c_double,
+                                                         P(ctypes.c_double), ctypes.c_double, i64, P(vp)], c_int),
+        "cfp_advdiff_config_default": ([P(AdvDiffConfig), i64], None),
+        "AdvectionDiffusionGMRES": ([P(AdvDiffConfig), P(AdvDiffResult), P(ctypes.c_double)], c_int),
+        "AdvectionDiffusionFFTDirect": ([P(AdvDiffConfig), P(AdvDiffResult), P(ctypes.c_double)], c_int),
         # unstructured meshes, the PCSHELL remap and the mesh transport loop (include/mesh_unstructured.h)
         "cfp_mesh_read_gmsh": ([cs, P(vp)], c_int),
         "cfp_mesh_create": ([i64, P(ctypes.c_double), i64, P(i64), P(i64), P(vp)], c_int),

@@ -112,6 +112,70 @@ double transport_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, s
 // the recurrence's rounding grows like eps / (1 - |a|): this cap keeps it near 1e-12
 constexpr double kZrecMaxRatio = 1.0 - 1.0 / 8192.0;
 
+// lambda (1 - w) + mu (2 - w - conj(w)), w = e^{-2 pi i k / n}: one axis' part of the
+// advection-diffusion symbol (0 for n == 1)
+std::vector<cd> host_advdiff_symbol(i64 n, std::complex<double> lam, std::complex<double> mu) {
+  std::vector<cd> s((size_t)n, make_cd(0.0, 0.0));
+  if (n <= 1) return s;
+  const std::vector<cd> hat = host_transport_symbol(n);
+  for (i64 k = 0; k < n; ++k) {
+    // the advection part exactly as the transport setter forms it (set_separable), so that mu = 0
+    // gives its tables bit for bit; 2 - w - conj(w) = 2 Re(1 - w)
+    const double re = hat[k].x * lam.real() - hat[k].y * lam.imag();
+    const double im = hat[k].x * lam.imag() + hat[k].y * lam.real();
+    const double c2 = 2.0 * hat[k].x;
+    s[k] = make_cd(re + mu.real() * c2, im + mu.imag() * c2);
+  }
+  return s;
+}
+
+// Along z the advection-diffusion symbol of a column, d - p e^{-i theta} - q e^{i theta} with
+// p = lamz + muz, q = muz, d = 1 + sx[kx] + sy[ky] + p + q, factors as
+// beta (1 - a e^{-i theta}) (1 - b e^{i theta}), beta the root of beta^2 - d beta + p q = 0 of
+// larger modulus, a = p / beta, b = q / beta (cfp_three_pass.hip k_tp_mid_rec2).  ratios = max |a|,
+// max |b| over the columns; beta = 0 gives infinity.
+std::complex<double> advdiff_z_beta(cd x, cd y, std::complex<double> p, std::complex<double> q) {
+  const std::complex<double> d = std::complex<double>(x.x + y.x + 1.0, x.y + y.y) + p + q;
+  if (q == 0.0) return d;  // first order: the roots are d and 0 (a is the transport ratio exactly)
+  std::complex<double> sq = std::sqrt(d * d - 4.0 * p * q);
+  if (d.real() * sq.real() + d.imag() * sq.imag() < 0.0) sq = -sq;  // the root on d's side is the larger
+  return 0.5 * (d + sq);
+}
+void advdiff_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz,
+                     std::complex<double> mz, double ratios[2]) {
+  const std::complex<double> p = lz + mz, q = mz;
+  const double pn = std::abs(p), qn = std::abs(q);
+  ratios[0] = ratios[1] = 0.0;
+  for (const cd& y : sy)
+    for (const cd& x : sx) {
+      const double bn = std::abs(advdiff_z_beta(x, y, p, q));
+      const double ra = bn > 0.0 ? pn / bn : (pn > 0.0 ? INFINITY : 0.0);
+      const double rb = bn > 0.0 ? qn / bn : (qn > 0.0 ? INFINITY : 0.0);
+      if (!(ra <= ratios[0])) ratios[0] = ra;
+      if (!(rb <= ratios[1])) ratios[1] = rb;
+    }
+}
+// k_tp_mid_rec2's column table at 256^3 (cfp_three_pass.h): [unit u][a, r = 256 / beta, b][lane],
+// lane = x + 8 y2 holding column kx = 8 (u % 32) + x, ky = u / 32 + 32 brev3(y2)
+std::vector<cd> advdiff_z_table(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz,
+                                std::complex<double> mz) {
+  const std::complex<double> p = lz + mz, q = mz;
+  std::vector<cd> t((size_t)kRec2TabLen);
+  for (int u = 0; u < 1024; ++u)
+    for (int lane = 0; lane < 64; ++lane) {
+      const int x = lane & 7, y2 = lane >> 3;
+      const int k2 = ((y2 & 1) << 2) | (y2 & 2) | (y2 >> 2);
+      const std::complex<double> be = advdiff_z_beta(sx[(size_t)(8 * (u % 32) + x)], sy[(size_t)(u / 32 + 32 * k2)], p, q);
+      const std::complex<double> a = p / be, b = q / be, r = 256.0 / be;
+      t[(size_t)((3 * u) * 64 + lane)] = make_cd(a.real(), a.imag());
+      t[(size_t)((3 * u + 1) * 64 + lane)] = make_cd(r.real(), r.imag());
+      t[(size_t)((3 * u + 2) * 64 + lane)] = make_cd(b.real(), b.imag());
+    }
+  return t;
+}
+// two scans, eps / ((1 - |a|) (1 - |b|)): this cap keeps 8 eps / (1 - r)^2 at 2.9e-11
+constexpr double kZrec2MaxRatio = 1.0 - 1.0 / 128.0;
+
 int ilog2_exact(i64 v) {
   if (v <= 0 || (v & (v - 1))) return -1;
   int l = 0;
@@ -185,6 +249,12 @@ struct cfp_plan_s {
   bool zrec_ok = false;
   double zrec_amax = 0.0;
   cd lamz = cfp::make_cd(0.0, 0.0);
+  // the advection-diffusion symbol's z factors (cfp_plan_set_symbol_advdiff with muz != 0):
+  // zrec2_ok = every column's |a| and |b| <= 1 - 2^-7, so the 256^3 P2 may solve z by the
+  // two-sided recurrence (k_tp_mid_rec2) from the columns' factors in zrec2_tab (device,
+  // advdiff_z_table; allocated with the first eligible symbol)
+  bool zrec2_ok = false;
+  cd* zrec2_tab = nullptr;
   bool external_x = false;  // x transformed by the caller (real plan): y/z passes only, no 1/N
   // long axes (n > 4096): four-step split n = n1 n2, both <= 4096 (0: a short axis).  Their
   // spectrum stays in position order p = m1 + n1 m2 for frequency m = m2 + n2 m1.
@@ -270,6 +340,11 @@ bool use_plane(const cfp_plan_s* p) {
   // 32^2 planes win: 32^3 at 65,300-71,500 against 39,400-43,000, profiles/r06z2_plane32_ab.txt)
   return p->schedule == CFP_SCHEDULE_AUTO && p->chunk_planes == 0 &&
          (p->n[0] == 100 || p->n[0] == 64 || p->n[0] == 32);
+}
+
+bool plan_zrec2(const cfp_plan_s* p) {
+  return p->zrec2_ok && p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
+         three_pass_zrec_shape((int)p->n[0], p->tp_shape);
 }
 
 // axis order of the 5-pass schedule: the last one is fused with the symbol
@@ -498,7 +573,8 @@ int run_apply(cfp_plan_s* p, const cd* diag_override, const cd* b, cd* x, hipStr
           a.zrec = 1;
           a.lamz = p->lamz;
         }
-        e = launch_three_pass(q.tp, tn, tin, tout, a, p->tp_shape, s);
+        if (q.tp == 1 && plan_zrec2(p)) e = launch_three_pass_rec2(tout, a, p->zrec2_tab, s);
+        else e = launch_three_pass(q.tp, tn, tin, tout, a, p->tp_shape, s);
       }
       g_stamp = LaunchStamp{};
       if (e != hipSuccess) return hip_error(e, "3-sweep launch");
@@ -655,7 +731,7 @@ int set_separable(cfp_plan_s* p, const std::vector<cd> hat[3], const double lam[
     }
   }
   ++p->sym_version;
-  p->zrec_ok = false;
+  p->zrec_ok = p->zrec2_ok = false;
   return upload_separable(p, s);
 }
 
@@ -738,6 +814,7 @@ extern "C" int cfp_plan_destroy(cfp_plan_t p) {
   }
   if (p->host_stage) hipFree(p->host_stage);
   if (p->mid_buf) hipFree(p->mid_buf);
+  if (p->zrec2_tab) hipFree(p->zrec2_tab);
   if (p->post_partial) hipFree(p->post_partial);
   if (p->pre_buf) hipFree(p->pre_buf);
   graph_clear(p);
@@ -771,7 +848,56 @@ extern "C" int cfp_plan_set_symbol_transport(cfp_plan_t p, const double lam[6]) 
 
 extern "C" int cfp_plan_mid_kernel(cfp_plan_t p, int* kind) {
   if (!p || !kind) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  *kind = plan_zrec(p) ? 1 : 0;
+  *kind = plan_zrec(p) ? CFP_MID_KERNEL_ZREC : (plan_zrec2(p) ? CFP_MID_KERNEL_ZREC2 : CFP_MID_KERNEL_FFT);
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_plan_set_symbol_advdiff(cfp_plan_t p, const double lam[6], const double mu[6]) {
+  if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  DeviceGuard dg(p->device);
+  // the separable tables in closed form (set_separable's product with lambda is folded in)
+  std::vector<cd> s[3];
+  for (int a = 0; a < 3; ++a) s[a] = host_advdiff_symbol(p->n[a], lamc(lam, a), lamc(mu, a));
+  ++p->sym_version;
+  p->zrec_ok = p->zrec2_ok = false;
+  int rc = upload_separable(p, s);
+  if (rc) return rc;
+  if (p->n[0] == 256 && p->n[1] == 256 && p->n[2] == 256) {  // the one grid the recurrence kernels are built for
+    const std::complex<double> lz = lamc(lam, 2), mz = lamc(mu, 2);
+    if (mz == 0.0) {
+      // first order along z: k_tp_mid_rec, which reads c from the column table
+      p->zrec_amax = transport_z_ratio(p->sym1d[0], p->sym1d[1], lz);
+      p->zrec_ok = p->zrec_amax <= kZrecMaxRatio;
+      p->lamz = make_cd(lz.real(), lz.imag());
+    } else {
+      double r[2];
+      advdiff_z_ratio(p->sym1d[0], p->sym1d[1], lz, mz, r);
+      if (r[0] <= kZrec2MaxRatio && r[1] <= kZrec2MaxRatio) {
+        const std::vector<cd> t = advdiff_z_table(p->sym1d[0], p->sym1d[1], lz, mz);
+        if (!p->zrec2_tab) HIPCHK(hipMalloc(&p->zrec2_tab, sizeof(cd) * t.size()));
+        HIPCHK(hipMemcpy(p->zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
+        p->zrec2_ok = true;
+      }
+    }
+  }
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_advdiff_symbol_1d(int64_t n, const double lam[2], const double mu[2], double* out) {
+  if (!lam || !mu || !out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  if (n < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "n must be >= 1");
+  std::vector<cd> s = host_advdiff_symbol(n, {lam[0], lam[1]}, {mu[0], mu[1]});
+  std::memcpy(out, s.data(), sizeof(cd) * (size_t)n);
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_advdiff_z_ratio(int64_t nx, int64_t ny, const double lam[6], const double mu[6],
+                                   double ratios[2]) {
+  if (!lam || !mu || !ratios) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  if (nx < 1 || ny < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
+  std::vector<cd> s[2] = {host_advdiff_symbol(nx, lamc(lam, 0), lamc(mu, 0)),
+                          host_advdiff_symbol(ny, lamc(lam, 1), lamc(mu, 1))};
+  advdiff_z_ratio(s[0], s[1], lamc(lam, 2), lamc(mu, 2), ratios);
   return CFP_SUCCESS;
 }
 
@@ -807,7 +933,7 @@ extern "C" int cfp_plan_set_diag(cfp_plan_t p, const double* diag, int on_device
   DeviceGuard dg(p->device);
   free_symbol(p);
   ++p->sym_version;
-  p->zrec_ok = false;
+  p->zrec_ok = p->zrec2_ok = false;
   HIPCHK(hipMalloc(&p->diag, sizeof(cd) * (size_t)p->N));
   HIPCHK(hipMemcpy(p->diag, diag, sizeof(cd) * (size_t)p->N, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   p->sym_kind = 2;

@@ -78,6 +78,12 @@ hipError_t launch_three_pass_fused(int stage, int n, const cd* in, cd* out, cons
 // the shapes whose P2 has the recurrence kernel (k_tp_mid_rec, TPArgs::zrec): 256^3, mid =
 // DEFAULT, y split 32 x 8.  SWAP64_PF is the same shape with the FFT kernel, always.
 bool three_pass_zrec_shape(int n, TPShape shape);
+// P2 (data in place) of those shapes for the advection-diffusion symbol: the two-sided
+// recurrence (k_tp_mid_rec2).  tab2 (device, 16-byte aligned): the z factors of every column,
+// [unit u][a, r = 256 / beta, b][lane], 1024 units of 64 lanes, lane = x + 8 y2 holding column
+// kx = 8 (u % 32) + x, ky = u / 32 + 32 brev3(y2); the caller has checked both z ratios
+constexpr int kRec2TabLen = 1024 * 3 * 64;
+hipError_t launch_three_pass_rec2(cd* data, const TPArgs& a, const cd* tab2, hipStream_t s);
 
 bool three_pass_supported(const i64 n[3]);
 // 100^3 (n = R^2, R = 10: cfp_three_pass_sq.hip); launch_three_pass routes n = 100 there.

@@ -18,6 +18,8 @@
 //       array and the same 8 rows x 128 B accesses (lane = x + 8 y2) without the z transforms:
 //       y2 DFT across lane bits 3..5, z solved as the recurrence u_z = a u_{z-1} + w_z in the
 //       registers of the lane that owns the column, one carry per wave)
+//       (k_tp_mid_rec2, the same for an advection-diffusion symbol with mu_z != 0 and both z
+//       ratios <= 1 - 2^-7: a forward and a backward recurrence, two carries per wave)
 //   P3  k_tp_rows<inv>: P1 on the conjugate, x 1/N
 //
 // P1/P3 workgroups are N1 x 16 threads x 16 points with a split-LDS exchange buffer of
@@ -1190,6 +1192,274 @@ k_tp_mid_rec(cd* data, TPArgs a, int nunits) {
   tp_mid_rec_body<PROBE, PF, LD>(data, a, nunits, pf_l, carr, ctab, tw_l);
 }
 
+// ---------------------------------------------------------------------------------------------
+// P2 for the advection-diffusion symbol with z solved by a two-sided recurrence (k_tp_mid_rec2;
+// 256^3, N2 = 8): tp_mid_rec_body's tile, access, y2 DFT and forward scan, then the same scan
+// backwards.  A function of its own, so that the transport kernel's code stays what it was.
+// With p = lamz + muz, q = muz and d = c + p + q the column's symbol is
+//   d - p e^{-i theta} - q e^{i theta} = beta (1 - a e^{-i theta}) (1 - b e^{i theta}),
+// beta the root of beta^2 - d beta + p q = 0 of larger modulus, a = p / beta, b = q / beta: the
+// forward system t_z = a t_{z-1} + w_z, w = v nz / beta, as in tp_mid_rec_body, then the backward
+// system u_z = b u_{z+1} + t_z the same way downwards: a register scan from slot 15 to 0, the
+// waves' block-start values F_w = s'_0 into the second carry array, a second workgroup barrier,
+// the carry
+//   U_{16 (w + 1)} = sum_k b^{16 k} F_{(w + 1 + k) mod 16} / (1 - b^256)   (Horner in b^16)
+// from the later waves, and b^{16-m} U added to slot m.  With two barriers per unit the carry
+// arrays need no unit parity (a wave that runs ahead into the next unit's forward write has passed
+// this unit's second barrier, behind every read of the forward array; the backward array likewise
+// behind the next unit's first), so the forward and the backward array share the 32 KiB and the
+// seven prefetched slots stay: 157 of 160 KiB with the table's third entry (b).
+//
+// The columns' a, r = 256 / beta and b (one complex square root each) come from the host, which
+// computes them when the symbol is set (cfp_plan.hip, [unit][a, r, b][lane], 3 MiB): wave 0
+// brings 3 KiB per unit by LDS-DMA straight into the table, two units ahead and issued with the
+// prefetch at the unit's end (a DMA pending across the next unit's loads would turn their counted
+// waits into vmcnt(0)); the next unit's first barrier publishes it.  Three buffers: the one
+// written at a unit's end was last read two units earlier.  The host enables the kernel where
+// max(|a|, |b|) <= 1 - 2^-7 on every column.
+template <int PROBE, bool PF, int LD>
+__device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TPArgs& a, int nunits,
+                                                 double* __restrict__ pf_l, cd* __restrict__ carr,
+                                                 cd* __restrict__ ctab, cd* __restrict__ tw_l,
+                                                 const cd* __restrict__ tab2) {
+  constexpr int TN = 256, N2 = 8, XT = 8, NXT = TN / XT, NW = 16;
+  constexpr int NPF = PF ? kRecNPF : 0;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, x = lane & 7, y2 = lane >> 3;
+  const int wv = __builtin_amdgcn_readfirstlane(tid / 64);
+  const i64 zs = (i64)TN << (a.lnyl ? a.lnyl : ilog2(TN));
+  // (idx, at, slot_ptr, prefetch, dif2, dit2, pin, cfma: as in tp_mid_rec_body)
+  const auto idx = [](int i) {
+    asm volatile("" : "+v"(i));
+    return i;
+  };
+  const auto at = [](cd* base, unsigned off) { return reinterpret_cast<cd*>(reinterpret_cast<char*>(base) + off); };
+  // unit u's a, r, b of the host's table -> ctab[buf] by LDS-DMA, lane-linear (wave 0)
+  const auto tab_fetch = [&](int u, int buf) {
+    unsigned lo = 16u * (unsigned)lane;
+    asm volatile("" : "+s"(u), "+v"(lo));
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+      __builtin_amdgcn_global_load_lds((glb_void_t*)at(const_cast<cd*>(tab2) + (i64)(3 * u + e) * 64, lo),
+                                       (lds_void_t*)(ctab + (3 * buf + e) * 64), 16, 0, 0);
+  };
+  if (tid < TN) tw_l[tid] = a.tw[tid];
+  if (wv == 0 && (int)blockIdx.x < nunits) {  // the first two units' tables
+    tab_fetch((int)blockIdx.x, 0);
+    if ((int)(blockIdx.x + gridDim.x) < nunits) tab_fetch((int)(blockIdx.x + gridDim.x), 1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+  const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);
+  const auto slot_ptr = [&](int u, int m) {
+    return data + ((u % NXT) * XT + (i64)TN * N2 * (u / NXT) + zs * (16 * wv + m));
+  };
+  const auto prefetch = [&](int u) {  // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
+    unsigned lo0 = loff;
+    asm volatile("" : "+s"(u), "+v"(lo0));
+#pragma unroll
+    for (int m = 0; m < NPF; ++m)
+      __builtin_amdgcn_global_load_lds((glb_void_t*)at(slot_ptr(u, m), lo0), (lds_void_t*)(pf_l + (wv * NPF + m) * 128),
+                                       16, 0, (LD & F_NT_LD) ? 2 : 0);
+  };
+  if constexpr (PF) {
+    if ((int)blockIdx.x < nunits) prefetch((int)blockIdx.x);
+  }
+  const double s3 = (y2 & 1) ? -1.0 : 1.0;
+  const cd w8 = a.tw[(TN / 8) * (y2 & 3)], w4 = a.tw[(TN / 4) * (y2 & 1)];
+  const auto dif2 = [](auto bit, cd& p, cd& q, cd w) {
+    constexpr int B = decltype(bit)::value;
+    swap_c<B>(p, q);
+    const cd s = cadd(p, q), d = cmul(csub(p, q), w);
+    p = s;
+    q = d;
+    swap_c<B>(p, q);
+  };
+  const auto dit2 = [](auto bit, cd& p, cd& q, cd w) {
+    constexpr int B = decltype(bit)::value;
+    swap_c<B>(p, q);
+    const cd t = cmul(q, w);
+    q = csub(p, t);
+    p = cadd(p, t);
+    swap_c<B>(p, q);
+  };
+  using bit5 = std::integral_constant<int, 5>;
+  using bit4 = std::integral_constant<int, 4>;
+  const auto pin = [](cd& w) { asm volatile("" : "+v"(w.x), "+v"(w.y)); };
+  const auto cfma = [](cd p, cd q, cd c) {
+    return make_cd(fma(p.x, q.x, fma(-p.y, q.y, c.x)), fma(p.x, q.y, fma(p.y, q.x, c.y)));
+  };
+  // the cyclic closure of a Horner sum: acc / (1 - P16^16), P16 the ratio's 16th power
+  const auto close = [](cd acc, cd P16) {
+    const cd P2 = cmul(P16, P16), P4 = cmul(P2, P2), P8 = cmul(P4, P4), P = cmul(P8, P8);
+    const cd d = make_cd(1.0 - P.x, -P.y);
+    const double id = 1.0 / fma(d.x, d.x, d.y * d.y);
+    return make_cd(fma(acc.x, d.x, acc.y * d.y) * id, fma(acc.y, d.x, -acc.x * d.y) * id);
+  };
+  const auto pow16 = [](cd t) {
+    const cd t2 = cmul(t, t), t4 = cmul(t2, t2), t8 = cmul(t4, t4);
+    return cmul(t8, t8);
+  };
+
+  // One unit.  MORE: another unit follows; the last unit is its own instantiation.
+  int buf = 0;
+  const auto unit = [&](const int it, auto more_c) {
+    constexpr bool more = decltype(more_c)::value;
+    const int u = it;
+    const int k1 = a.k1_off + u / NXT;  // global k1
+    const int nbuf = buf == 2 ? 0 : buf + 1;
+    cd v[16];
+    if constexpr (PROBE & PR_NO_LOAD) {
+#pragma unroll
+      for (int m = 0; m < 16; ++m) v[m] = make_cd(lane + m, wv + u);
+    } else {
+      if constexpr (PF) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA landed
+#pragma unroll
+        for (int m = 0; m < NPF; ++m)
+          v[m] = fromv(*reinterpret_cast<const dv2*>(pf_l + (wv * NPF + m) * 128 + 2 * idx(lane)));
+      }
+      {
+        int ul = u;
+        unsigned lo1 = loff;
+        asm volatile("" : "+s"(ul), "+v"(lo1));  // scalar base + this register, formed here
+#pragma unroll
+        for (int m = NPF; m < 16; ++m) v[m] = gload<LD>(at(slot_ptr(ul, m), lo1));
+      }
+    }
+    // twiddle W_256^{y2 k1}
+    {
+      const cd w = tw_l[((idx(lane) >> 3) * k1) & (TN - 1)];
+#pragma unroll
+      for (int m = 0; m < 16; ++m) v[m] = cmul(v[m], w);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // y2 DFT across lane bits 5, 4, 3 (DIF): lane (x, y2) ends as frequency k2 = brev3(y2)
+    if constexpr (!(PROBE & PR_NO_Y2)) {
+#pragma unroll
+      for (int m = 0; m < 16; m += 2) {
+        dif2(bit5{}, v[m], v[m + 1], w8);
+        dif2(bit4{}, v[m], v[m + 1], w4);
+        v[m] = bfly_l3(v[m], s3);
+        v[m + 1] = bfly_l3(v[m + 1], s3);
+        pin(v[m]);
+        pin(v[m + 1]);
+        if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if constexpr (!(PROBE & PR_NO_ZMATH)) {
+      const int ln = idx(lane);
+      // forward: s_m = a s_{m-1} + v_m, t_m = r s_m + a^{m+1} (carry into the wave)
+      const cd aa = ctab[(3 * buf) * 64 + ln];  // this lane's column (x, k2)
+#pragma unroll
+      for (int m = 1; m < 16; ++m) v[m] = cfma(aa, v[m - 1], v[m]);
+      const cd E = cmul(ctab[(3 * buf + 1) * 64 + ln], v[15]);
+      carr[wv * 64 + ln] = E;  // the wave's block-end value t_15 of this column
+#pragma unroll
+      for (int m = 0; m < 16; ++m) pin(v[m]);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // wave 0: the table DMA of the previous unit's end has landed
+      lds_barrier();  // every wave's block-end values are in carr[0]
+      {
+        const cd A = pow16(aa);
+        cd acc = E;  // E_wv
+#pragma unroll
+        for (int k = 14; k >= 0; --k) {
+          acc = cfma(acc, A, carr[((wv - 1 - k) & 15) * 64 + ln]);
+          if ((k & 3) == 0) __builtin_amdgcn_sched_barrier(0);  // 4 reads in flight, not 16
+        }
+        const cd r = ctab[(3 * buf + 1) * 64 + ln];
+        cd g = cmul(aa, close(acc, A));
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+          v[m] = cfma(r, v[m], g);
+          if (m < 15) g = cmul(aa, g);
+        }
+      }
+      // backward: s'_m = b s'_{m+1} + t_m, u_m = s'_m + b^{16-m} (carry from the later waves)
+      const cd bb = ctab[(3 * buf + 2) * 64 + ln];
+#pragma unroll
+      for (int m = 14; m >= 0; --m) v[m] = cfma(bb, v[m + 1], v[m]);
+      carr[(NW + wv) * 64 + ln] = v[0];  // the wave's block-start value of this column
+#pragma unroll
+      for (int m = 0; m < 16; ++m) pin(v[m]);
+      lds_barrier();  // every wave's block-start values are in carr[1]
+      {
+        const cd B = pow16(bb);
+        cd acc = v[0];  // F_wv
+#pragma unroll
+        for (int k = 14; k >= 0; --k) {
+          acc = cfma(acc, B, carr[(NW + ((wv + 1 + k) & 15)) * 64 + ln]);
+          if ((k & 3) == 0) __builtin_amdgcn_sched_barrier(0);
+        }
+        cd g = cmul(bb, close(acc, B));
+#pragma unroll
+        for (int m = 15; m >= 0; --m) {
+          v[m] = cadd(v[m], g);
+          if (m > 0) g = cmul(bb, g);
+        }
+      }
+    }
+    // inverse y2 DFT on the conjugate, conjugate twiddle, then the DMAs and this unit's stores
+    {
+      int k1s = k1, us = u;
+      unsigned lo2 = loff;
+      asm volatile("" : "+s"(k1s), "+s"(us), "+v"(lo2));
+      const cd w = tw_l[((idx(lane) >> 3) * k1s) & (TN - 1)];
+#pragma unroll
+      for (int m = 0; m < 16; m += 2) {
+        cd p = cconj(v[m]), q = cconj(v[m + 1]);
+        if constexpr (!(PROBE & PR_NO_Y2)) {
+          p = bfly_l3(p, s3);
+          q = bfly_l3(q, s3);
+          dit2(bit4{}, p, q, w4);
+          dit2(bit5{}, p, q, w8);
+        }
+        v[m] = cconj(cmul(p, w));
+        v[m + 1] = cconj(cmul(q, w));
+        pin(v[m]);
+        pin(v[m + 1]);
+        if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
+      }
+      // behind all of this unit's arithmetic and in front of its stores: the next unit's prefetch
+      // and the table of the unit after it (nobody reads that buffer any more: its last readers
+      // passed this unit's second barrier)
+      if constexpr (more) {
+        if constexpr (PF && !(PROBE & PR_NO_LOAD)) prefetch(it + (int)gridDim.x);
+        if (wv == 0 && it + 2 * (int)gridDim.x < nunits) tab_fetch(it + 2 * (int)gridDim.x, nbuf == 2 ? 0 : nbuf + 1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (!(PROBE & PR_NO_STORE)) {
+#pragma unroll
+        for (int m = 0; m < 16; ++m) gstore<0>(at(slot_ptr(us, m), lo2), v[m]);
+      }
+      if constexpr (PROBE & PR_NO_STORE) {
+        double acc = 0.0;
+#pragma unroll
+        for (int m = 0; m < 16; ++m) acc += v[m].x + v[m].y;
+        if (acc == 1.2345e300) *at(slot_ptr(us, 0), lo2) = make_cd(acc, 0.0);  // keeps the work live, never true
+      }
+    }
+    buf = nbuf;
+  };
+  int it = blockIdx.x;
+  for (; it + (int)gridDim.x < nunits; it += gridDim.x) unit(it, std::true_type{});
+  if (it < nunits) unit(it, std::false_type{});
+}
+
+// the kernel of tp_mid_rec2_body: tab2 the columns' a, r, b (cfp_three_pass.h)
+template <int PROBE = 0, bool PF = false, int LD = 0, int TAG = 0>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
+k_tp_mid_rec2(cd* data, TPArgs a, int nunits, const cd* tab2) {
+#ifndef CFP_KEXP
+  static_assert(PROBE == 0, "timing probes are built in tools/kexp only");
+#endif
+  __shared__ __attribute__((aligned(16))) double pf_l[PF ? 16 * kRecNPF * 128 : 2];
+  __shared__ __attribute__((aligned(16))) cd carr[2 * 16 * 64];  // [forward block ends, backward block starts][wave][column]
+  __shared__ __attribute__((aligned(16))) cd ctab[3 * 3 * 64];   // the columns' a, r and b [unit mod 3][a, r, b][column]
+  __shared__ cd tw_l[256];
+  tp_mid_rec2_body<PROBE, PF, LD>(data, a, nunits, pf_l, carr, ctab, tw_l, tab2);
+}
+
 
 bool three_pass_supported(const i64 n[3]) {
   return n[0] == n[1] && n[1] == n[2] && (n[0] == 128 || n[0] == 256 || n[0] == 512);
@@ -1594,6 +1864,20 @@ static void launch_mid_rec(cd* data, const TPArgs& a, hipStream_t s) {
     TP_LAUNCH((k_tp_mid_rec<0, PF, kP2LoadFlags, 1>), dim3(grid_of(units, 1)), dim3(1024), s, data, a, units);
   else
     TP_LAUNCH((k_tp_mid_rec<0, PF, kP2LoadFlags>), dim3(grid_of(units, 1)), dim3(1024), s, data, a, units);
+}
+
+hipError_t launch_three_pass_rec2(cd* data, const TPArgs& a, const cd* tab2, hipStream_t s) {
+  constexpr int units = (256 / 8) * (256 / 8);  // x tiles x k1
+  const bool pf = ((uintptr_t)data & 15) == 0;  // the LDS-DMA prefetch takes 16-byte addresses
+  const dim3 g(grid_of(units, 1)), b(1024);
+  if (a.krylov) {
+    if (pf) TP_LAUNCH((k_tp_mid_rec2<0, true, kP2LoadFlags, 1>), g, b, s, data, a, units, tab2);
+    else TP_LAUNCH((k_tp_mid_rec2<0, false, kP2LoadFlags, 1>), g, b, s, data, a, units, tab2);
+  } else {
+    if (pf) TP_LAUNCH((k_tp_mid_rec2<0, true, kP2LoadFlags>), g, b, s, data, a, units, tab2);
+    else TP_LAUNCH((k_tp_mid_rec2<0, false, kP2LoadFlags>), g, b, s, data, a, units, tab2);
+  }
+  return hipGetLastError();
 }
 
 bool three_pass_slab_supported(const i64 n[3], int P) {

@@ -223,6 +223,11 @@ struct CFP_INTERNAL ShellBase {
   uint64_t diag_version = 0;
   PetscInt solves_own = 0, solves_diag = 0;  // solve_3D calls per path (MatFFTHIPGetSolveCounts)
   PetscInt fused_ba = 0;                     // applyBA calls that took pc_fused_ba (MatFFTHIPGetFusedBACount)
+  // the advection-diffusion numbers (lam[6], mu[6]) the diffusion boundary last set on the plan
+  // (diffusion_cartesian.cpp) and the symbol version right after: equal numbers reuse the symbol
+  bool has_ad = false;
+  double ad[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t ad_version = 0;
 
   explicit ShellBase(int m) : magic(m) {}
   uint64_t symbol_version() const {
@@ -263,6 +268,10 @@ CFP_INTERNAL PetscErrorCode pc_solve(PC pc, FFTPrecTransportContext* ctx, Vec X,
 // y = B A x as one fused apply, where the build has one and this PC, A and x allow it (no remaps,
 // x != y: checked by the caller); *taken says whether y was written
 CFP_INTERNAL PetscErrorCode pc_fused_ba(PC pc, FFTPrecTransportContext* ctx, Mat A, Vec x, Vec y, bool* taken);
+
+// defined by the complex build (pcshell_fft3d.cpp): X = C^{-1} b with the plan's own symbol,
+// whatever set it (one apply of FFT_MAT's plan; b may be X) -- the diffusion direct solver
+CFP_INTERNAL PetscErrorCode own_symbol_apply(Mat FFT_MAT, Vec X, Vec b);
 
 // defined by pcshell_boundary.cpp
 CFP_INTERNAL PetscErrorCode shell_base(Mat A, ShellBase** out);  // the context of an FFT matrix of this build

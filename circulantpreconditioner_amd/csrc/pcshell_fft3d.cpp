@@ -334,6 +334,16 @@ extern "C" PetscErrorCode FftTransportSolver(PetscInt nx, PetscInt ny, PetscInt 
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 
+PetscErrorCode cfp_pc::own_symbol_apply(Mat FFT_MAT, Vec X, Vec b) {
+  FFTShell* s;
+  PetscCall(shell_of(FFT_MAT, &s));
+  PetscCall(check_size(X, s->nl, "own_symbol_apply: X has the wrong size"));
+  PetscCall(check_size(b, s->nl, "own_symbol_apply: b has the wrong size"));
+  ++s->solves_own;
+  PetscCall(shell_apply(s, X, b, true, nullptr));
+  return PETSC_SUCCESS;
+}
+
 // ------------------------------------------------------------------ PCSHELL callbacks
 // the solve of applyFFT3DPrecTransport (pcshell_boundary.cpp)
 PetscErrorCode cfp_pc::pc_solve(PC pc, FFTPrecTransportContext* ctx, Vec X, Vec src) {

@@ -21,14 +21,9 @@
 #include "../../include/circulant_fft.h"
 #include "../../include/pcshell_fft3d.h"
 #include "../../include/transport_equation.h"
+#include "gmres_time_loop.h"
 
-namespace {
-double wall() {
-  struct timeval tv;
-  gettimeofday(&tv, nullptr);
-  return (double)tv.tv_sec + 1e-6 * (double)tv.tv_usec;
-}
-}  // namespace
+using cfp_loop::wall;
 
 // One row per cell; the six faces of cell (i,j,k) in the order -x,+x,-y,+y,-z,+z with outward
 // normals; un = n . a.  Interior face: un > 0 adds dt |F|/|C| un to the diagonal (:109-110);
@@ -294,56 +289,8 @@ extern "C" PetscErrorCode TransportEquationGMRES(const cfp_transport_config* cfg
     PetscCheck(cfp_stream_sync(nullptr) == CFP_SUCCESS, PETSC_COMM_SELF, PETSC_ERR_LIB, "stream sync failed");
   res->setup_seconds = wall() - t_setup;
 
-  int64_t it = 0;
-  double time = 0.0;
-  bool stationary = false;
-  res->all_converged = 1;
-  res->min_step_its = -1;
-  if (cfg->profile) PetscCall(PetscMiniProfileBegin(1 << 16));
-  const double t_loop = wall();
-  while (it < cfg->ntmax && time <= cfg->tmax && !stationary) {  // :131
-    PetscCall(VecCopy(Un, dUn));
-    const double v = wall();
-    PetscCall(KSPSolve(ksp, Un, Un));
-    const double w = wall();
-    PetscCall(VecAXPY(dUn, -1.0, Un));
-    time += dt;
-    it += 1;
-    PetscReal norm;
-    PetscCall(VecNorm(dUn, NORM_2, &norm));
-    stationary = norm < cfg->precision;
-    KSPConvergedReason reason;
-    PetscInt its;
-    PetscReal residu;
-    PetscCall(KSPGetConvergedReason(ksp, &reason));
-    PetscCall(KSPGetIterationNumber(ksp, &its));
-    PetscCall(KSPGetResidualNorm(ksp, &residu));
-    PetscInt calls;
-    PetscLogDouble pcs;
-    PetscCall(KSPMiniGetPCApplyStats(ksp, &calls, &pcs));
-    res->solve_seconds += w - v;
-    res->pc_seconds += pcs;
-    res->pc_calls += calls;
-    res->total_its += its;
-    res->max_step_its = std::max<int64_t>(res->max_step_its, its);
-    res->min_step_its = res->min_step_its < 0 ? its : std::min<int64_t>(res->min_step_its, its);
-    res->last_reason = (int)reason;
-    res->last_residual = residu;
-    res->last_norm_dU = norm;
-    if (reason != KSP_CONVERGED_RTOL && reason != KSP_CONVERGED_ATOL) res->all_converged = 0;  // :166
-    PetscInt fd, fn;
-    PetscCall(KSPMiniGetFusedCounts(ksp, &fd, &fn));
-    res->fused_dots += fd;
-    res->fused_norms += fn;
-  }
-  res->loop_seconds = wall() - t_loop;
-  if (cfg->profile) {
-    PetscCall(PetscMiniProfileEnd(res->dev_ms, res->dev_launches));
-    res->dev_ms[0] = 1e3 * res->pc_seconds;
-    res->dev_launches[0] = res->pc_calls;
-  }
-  res->steps = it;
-  res->time = time;
+  // the time loop (:131-170), shared with AdvectionDiffusionGMRES
+  PetscCall(cfp_loop::gmres_time_loop(ksp, Un, dUn, dt, cfg->ntmax, cfg->tmax, cfg->precision, cfg->profile, res));
   if (U_out) {  // this rank's rows (all of them on one rank)
     const PetscScalar* u;
     PetscCall(VecGetArrayRead(Un, &u));

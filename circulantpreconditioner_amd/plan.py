@@ -115,6 +115,12 @@ class CirculantPlan:
         check(lib().cfp_plan_set_symbol_transport(self._h, _lam6(lam)))
         return self
 
+    def set_advdiff_symbol(self, lam: Sequence, mu: Sequence) -> "CirculantPlan":
+        """Diag = 1 + sum_d [lambda_d (1 - w_d) + mu_d (2 - w_d - conj(w_d))], w_d = e^{-2 pi i k_d/n_d}:
+        upwind advection numbers lambda_d = a_d dt / h_d, diffusion numbers mu_d = nu dt / h_d^2."""
+        check(lib().cfp_plan_set_symbol_advdiff(self._h, _lam6(lam), _lam6(mu)))
+        return self
+
     def set_separable_symbol(self, cx_hat, cy_hat, cz_hat, lam: Sequence) -> "CirculantPlan":
         """Diag = 1 + lx*tile(cx_hat) + ly*repeat(tile(cy_hat)) + lz*repeat(cz_hat)."""
         arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.complex128).reshape(-1)) for a in (cx_hat, cy_hat, cz_hat)]
@@ -276,10 +282,11 @@ class CirculantPlan:
 
     def mid_kernel(self) -> str:
         """The middle kernel the next apply launches: 'zrec' (z by recurrence: 256^3, default
-        shape, a transport symbol with z ratio <= 1 - 2^-13) or 'fft'."""
+        shape, a transport symbol with z ratio <= 1 - 2^-13), 'zrec2' (the two-sided recurrence:
+        an advection-diffusion symbol with mu_z != 0 and both z ratios <= 1 - 2^-7) or 'fft'."""
         k = ctypes.c_int()
         check(lib().cfp_plan_mid_kernel(self._h, ctypes.byref(k)))
-        return "zrec" if k.value == 1 else "fft"
+        return {1: "zrec", 2: "zrec2"}.get(k.value, "fft")
 
     def time_passes(self, b: torch.Tensor, x: torch.Tensor, iters: int = 20, stream=None) -> list:
         """Mean device time (ms) of each launch of one apply, HIP events on `stream`."""
@@ -333,6 +340,23 @@ def transport_symbol_1d(n: int) -> np.ndarray:
     out = np.empty(int(n), dtype=np.complex128)
     check(lib().cfp_transport_symbol_1d(int(n), out.ctypes.data))
     return out
+
+
+def advdiff_symbol_1d(n: int, lam: complex, mu: complex) -> np.ndarray:
+    """One axis' part of the advection-diffusion symbol: lam (1 - w) + mu (2 - w - conj(w))."""
+    out = np.empty(int(n), dtype=np.complex128)
+    l, m = complex(lam), complex(mu)
+    check(lib().cfp_advdiff_symbol_1d(int(n), (ctypes.c_double * 2)(l.real, l.imag),
+                                      (ctypes.c_double * 2)(m.real, m.imag), out.ctypes.data))
+    return out
+
+
+def advdiff_z_ratio(nx: int, ny: int, lam: Sequence, mu: Sequence) -> tuple:
+    """(max |a|, max |b|) over the (kx, ky) columns of the symbol's z factorisation
+    beta (1 - a e^{-i theta}) (1 - b e^{i theta}); no GPU needed."""
+    r = (ctypes.c_double * 2)()
+    check(lib().cfp_advdiff_z_ratio(int(nx), int(ny), _lam6(lam), _lam6(mu), r))
+    return float(r[0]), float(r[1])
 
 
 def pointwise_divide(w: torch.Tensor, x: torch.Tensor, y: torch.Tensor, stream=None) -> torch.Tensor:

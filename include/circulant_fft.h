@@ -70,6 +70,13 @@ int cfp_plan_destroy(cfp_plan_t plan);
  * lam = {lx.re, lx.im, ly.re, ly.im, lz.re, lz.im}.  Axes with n_d == 1 contribute 0
  * (build_transport_col leaves a size-1 column zero, src/FftLinearSolver_3D.c:83). */
 int cfp_plan_set_symbol_transport(cfp_plan_t plan, const double lam[6]);
+/* Advection-diffusion symbol in closed form, w_d = e^{-2 pi i k_d / n_d}:
+ *   Diag[k] = 1 + sum_d [ lambda_d (1 - w_d) + mu_d (2 - w_d - conj(w_d)) ],
+ * lambda_d = a_d dt / h_d the upwind advection number, mu_d = nu dt / h_d^2 the diffusion number
+ * (the reference's to-do: "ajouter l'equation de diffusion"); lam and mu are laid out as lam
+ * above, axes with n_d == 1 contribute 0, and mu = 0 is the transport symbol, bit for bit.  It
+ * fills the separable tables, so every schedule serves it. */
+int cfp_plan_set_symbol_advdiff(cfp_plan_t plan, const double lam[6], const double mu[6]);
 /* Separable symbol from caller-given 1-D eigenvalue vectors (host arrays of n_x, n_y, n_z
  * complex values, e.g. the 1-D DFTs of arbitrary circulant columns):
  * Diag = 1 + lx*tile(cx_hat) + ly*repeat(tile(cy_hat)) + lz*repeat(cz_hat)   (:136-164). */
@@ -182,11 +189,15 @@ int cfp_plan_set_schedule(cfp_plan_t plan, int schedule);
 #define CFP_TP_MID_SWAP64_PF 4 /* SWAP64 + LDS-DMA prefetch of half the next unit */
 int cfp_plan_set_three_pass_shape(cfp_plan_t plan, int n1, int mid);
 /* The middle kernel the plan's next apply launches: 0 the FFT kernel (or a schedule without a
- * middle kernel), CFP_MID_KERNEL_ZREC the z recurrence.  The recurrence runs at 256^3 under the
- * default shape for a symbol set by cfp_plan_set_symbol_transport whose z ratio
- * (cfp_transport_z_ratio) is at most 1 - 2^-13; CFP_TP_MID_SWAP64_PF is the FFT kernel always. */
+ * middle kernel), CFP_MID_KERNEL_ZREC the z recurrence, CFP_MID_KERNEL_ZREC2 the two-sided z
+ * recurrence.  The recurrence runs at 256^3 under the default shape for a symbol set by
+ * cfp_plan_set_symbol_transport (or cfp_plan_set_symbol_advdiff with mu_z == 0) whose z ratio
+ * (cfp_transport_z_ratio) is at most 1 - 2^-13; the two-sided one for a symbol set by
+ * cfp_plan_set_symbol_advdiff with mu_z != 0 whose two z ratios (cfp_advdiff_z_ratio) are both
+ * at most 1 - 2^-7; CFP_TP_MID_SWAP64_PF is the FFT kernel always. */
 #define CFP_MID_KERNEL_FFT 0
 #define CFP_MID_KERNEL_ZREC 1
+#define CFP_MID_KERNEL_ZREC2 2
 int cfp_plan_mid_kernel(cfp_plan_t plan, int *kind);
 
 /* Introspection: number of kernel launches of one apply, and per-launch timing.
@@ -221,6 +232,16 @@ int cfp_transport_symbol_1d(int64_t n, double *out_host);
  * s_d = lam_d * cfp_transport_symbol_1d(n_d): along z the transport symbol is the first-order
  * recurrence u_z = a u_{z-1} + w_z with that ratio a per column.  Infinity if a denominator is 0. */
 int cfp_transport_z_ratio(int64_t nx, int64_t ny, const double lam[6], double *amax_host);
+/* host: out[k] = lam (1 - w) + mu (2 - w - conj(w)), w = e^{-2 pi i k/n} (0 for n == 1), n complex
+ * values: one axis' part of the advection-diffusion symbol */
+int cfp_advdiff_symbol_1d(int64_t n, const double lam[2], const double mu[2], double *out_host);
+/* host (no GPU needed): along z the advection-diffusion symbol of column (kx, ky) is
+ * d - p e^{-i theta} - q e^{i theta} = beta (1 - a e^{-i theta}) (1 - b e^{i theta}) with
+ * p = lam_z + mu_z, q = mu_z, d = 1 + s_x[kx] + s_y[ky] + p + q, beta the root of
+ * beta^2 - d beta + p q = 0 of larger modulus, a = p / beta, b = q / beta: a forward and a backward
+ * first-order recurrence.  ratios_host = {max |a|, max |b|} over the columns; infinity where
+ * beta is 0. */
+int cfp_advdiff_z_ratio(int64_t nx, int64_t ny, const double lam[6], const double mu[6], double ratios_host[2]);
 
 #ifdef __cplusplus
 }

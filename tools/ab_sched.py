@@ -3,6 +3,8 @@
 
   python tools/ab_sched.py 100 plane three:0,default three:0,lane64 three:0,lane32 five
   python tools/ab_sched.py 256 real:three real:three_alt     # RealPlan schedules on the real part of b
+  python tools/ab_sched.py 256 three:0,default three:0,swap64pf --lam 0.6 0.15 0.6 --mu 0.2 0.2 2.5
+                                                             # the advection-diffusion symbol: zrec2 against fft
 
 Every variant applies the same b (SplitMix64 U[-1,1) complex, the bench's transport symbol) in
 place on the current stream, timed with HIP events over `--iters` back-to-back applies; the
@@ -27,6 +29,8 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--lam", type=float, nargs=3, default=[0.6, 0.15, 0.02])
+    ap.add_argument("--mu", type=float, nargs=3, default=None,
+                    help="diffusion numbers: the complex plans take set_advdiff_symbol(lam, mu)")
     ap.add_argument("--lib", default=None, help="another build of libcirculant_fft.so (A/B of two builds)")
     args = ap.parse_args()
     if args.lib:
@@ -47,7 +51,10 @@ def main() -> int:
             plans.append(p)
             continue
         p = cp.CirculantPlan(n)
-        p.set_transport_symbol(tuple(args.lam))
+        if args.mu is not None:
+            p.set_advdiff_symbol(tuple(args.lam), tuple(args.mu))
+        else:
+            p.set_transport_symbol(tuple(args.lam))
         sched, _, shape = v.partition(":")
         p.set_schedule(sched)
         if shape:
@@ -63,6 +70,8 @@ def main() -> int:
             res[v]["stage_ms"] = [round(t, 4) for t in p.time_passes(br, torch.empty_like(br), iters=20)]
         else:
             res[v]["passes"] = [q["mode"] for q in p.passes()]
+            res[v]["mid_kernel"] = p.mid_kernel()
+            res[v]["stage_ms"] = [round(t, 4) for t in p.time_passes(b, torch.empty_like(b), iters=50)]
         x = p.apply(br if real else b)
         r = ref.setdefault(real, x)
         res[v]["rel_diff"] = float((x - r).abs().max() / r.abs().max())
