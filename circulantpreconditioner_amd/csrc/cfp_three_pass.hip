@@ -85,6 +85,14 @@ __device__ __forceinline__ int xcd_unit(int it, int G) {
   return it - b + (b & 7) * (G >> 3) + (b >> 3);
 }
 
+// Opaque copy of a thread or lane index: what is derived from it is recomputed at its use
+// instead of living in a register across an FFT or a unit (every kernel of this file holds its
+// points plus one stage's temporaries in 128 VGPRs, and an address or index kept live spills)
+__device__ __forceinline__ int idx(int i) {
+  asm volatile("" : "+v"(i));
+  return i;
+}
+
 // a byte load with the sweep's load policy (the fused stencil's row classes)
 template <int FLAGS>
 __device__ __forceinline__ unsigned char gload_u8(const unsigned char* p) {
@@ -210,12 +218,8 @@ k_tp_rows(const cd* in, cd* out, TPArgs a, int nunits) {
   // phase A: column x, thread ty of TY
   const int x0 = LP ? (tid & 31) + 32 * (tid >> 6) : tid % TN, ty0 = LP ? (tid >> 5) & 1 : tid / TN;
   const int r0 = tid / TR, tx0 = tid % TR;  // phase C: row r, thread tx of TR
-  // fresh (laundered) index copies at every use, as in k_tp_mid: nothing but the points
+  // fresh (laundered) index copies (idx) at every use, as in k_tp_mid: nothing but the points
   // stays live across an FFT
-  const auto idx = [](int i) {
-    asm volatile("" : "+v"(i));
-    return i;
-  };
   // rows of the chunked side (P1 output, P3 input): one GPU: nyl = TN, one chunk = natural
   const int lnyl = a.lnyl ? a.lnyl : ilog2(TN);
   const int nyl = 1 << lnyl;
@@ -696,10 +700,6 @@ k_tp_mid_sw(cd* data, TPArgs a, int nunits) {
   const int tz0 = T == 64 ? tid / 64 : 2 * (tid >> 6) + ((lane0 >> 2) & 1);
   // rows of this rank's block [TN z][nyl][NX] (one GPU: nyl = TN); unit u = (x tile, local k1)
   const i64 zs = (i64)NX << (a.lnyl ? a.lnyl : ilog2(TN));
-  const auto idx = [](int i) {
-    asm volatile("" : "+v"(i));
-    return i;
-  };
   // this lane's first point and the twiddle W_TN^{y2 k1} (natural layout: x = c % XT, y2 = c / XT)
   const auto col_ptr = [&](int u, int c, int tz) {
     const int xt = u % NXT, k1 = u / NXT;
@@ -947,6 +947,107 @@ k_tp_mid_sw(cd* data, TPArgs a, int nunits) {
 // reads carry the information that they do not alias the prefetch buffer, without which the
 // compiler waits for every LDS-DMA in flight (vmcnt(0)) before the first LDS read that follows.
 constexpr int kRecNPF = 7;  // slots that come from the LDS prefetch (154 of 160 KiB LDS)
+
+// What the recurrence bodies (tp_mid_rec_body, tp_mid_rec2_body) share: each helper is defined
+// here once and compiles to the instructions the bodies held as lambdas of their own (compare
+// with tools/isa_same.py).  They take and return values or single points, never the 16-slot
+// array: with the y2 loops moved whole into functions of cd (&v)[16], k_tp_mid_rec went from 118
+// VGPRs without scratch to 128 with 68 spilled (180 B of scratch), k_tp_mid_rec2 to 26-30 spilled.
+namespace rec {
+__device__ __forceinline__ cd* at(cd* base, unsigned off) {
+  return reinterpret_cast<cd*>(reinterpret_cast<char*>(base) + off);
+}
+// Radix-2 stage over lane bit B (5 or 4) on the slot pair (p, q): the swap gives the lower lane
+// both lanes' p and the upper lane both lanes' q, each lane runs one whole butterfly (no
+// duplicated value, no half thrown away), and the second swap hands every lane its own results
+// back: sums to the lower lane, differences to the upper.  DIF: a + b, (a - b) w.
+template <int B>
+__device__ __forceinline__ void dif2(cd& p, cd& q, cd w) {
+  swap_c<B>(p, q);
+  const cd s = cadd(p, q), d = cmul(csub(p, q), w);
+  p = s;
+  q = d;
+  swap_c<B>(p, q);
+}
+// DIT: a + b w, a - b w
+template <int B>
+__device__ __forceinline__ void dit2(cd& p, cd& q, cd w) {
+  swap_c<B>(p, q);
+  const cd t = cmul(q, w);
+  q = csub(p, t);
+  p = cadd(p, t);
+  swap_c<B>(p, q);
+}
+// pin(): the values are formed where the source forms them.  Sunk towards their uses, a DFT's
+// or a column's last operations keep their inputs live as well and the kernel goes to scratch.
+__device__ __forceinline__ void pin(cd& w) { asm volatile("" : "+v"(w.x), "+v"(w.y)); }
+// p q + c in 4 fused operations
+__device__ __forceinline__ cd cfma(cd p, cd q, cd c) {
+  return make_cd(fma(p.x, q.x, fma(-p.y, q.y, c.x)), fma(p.x, q.y, fma(p.y, q.x, c.y)));
+}
+// One slot pair of the y2 DFT across lane bits 5, 4, 3 (DIF): lane (x, y2) ends as frequency
+// k2 = brev3(y2).  The per-lane constants: the stage twiddles w8 = W_8^{y2 & 3} (lane bit 5) and
+// w4 = W_4^{y2 & 1} (lane bit 4), which the two lanes of a pair share, and the sign s3 of the DPP
+// stage (+1 where lane bit 3 is clear, -1 where set).
+__device__ __forceinline__ void y2_fwd_pair(cd& p, cd& q, cd w8, cd w4, double s3) {
+  dif2<5>(p, q, w8);
+  dif2<4>(p, q, w4);
+  p = bfly_l3(p, s3);
+  q = bfly_l3(q, s3);
+  pin(p);
+  pin(q);
+}
+// One slot pair of the inverse y2 DFT on the conjugate (DIT over lane bits 3, 4, 5: bit-reversed
+// in, natural out), then the conjugate twiddle w = W_256^{y2 k1}
+template <int PROBE>
+__device__ __forceinline__ void y2_inv_pair(cd& vp, cd& vq, cd w, cd w8, cd w4, double s3) {
+  cd p = cconj(vp), q = cconj(vq);
+  if constexpr (!(PROBE & PR_NO_Y2)) {
+    p = bfly_l3(p, s3);
+    q = bfly_l3(q, s3);
+    dit2<4>(p, q, w4);
+    dit2<5>(p, q, w8);
+  }
+  vp = cconj(cmul(p, w));
+  vq = cconj(cmul(q, w));
+  pin(vp);
+  pin(vq);
+}
+// A unit's memory access.  A point's address = a wave-uniform base (unit u = (x tile, local k1):
+// row 8 k1; slot m: z = 16 wv + m) + this lane's 32-bit byte offset loff (x, row y2): a scalar
+// base plus one offset register for all 16 slots, instead of 16 address pairs.  The callers pass
+// opaque copies of u and loff, so that the addresses are formed again at each phase.
+struct Tile {
+  static constexpr int TN = 256, N2 = 8, XT = 8, NXT = TN / XT;
+  cd* data;
+  i64 zs;
+  int wv;
+  double* pf_l;
+  __device__ __forceinline__ cd* slot_ptr(int u, int m) const {
+    return data + ((u % NXT) * XT + (i64)TN * N2 * (u / NXT) + zs * (16 * wv + m));
+  }
+  // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
+  template <int NPF, int LD>
+  __device__ __forceinline__ void prefetch(int u, unsigned loff) const {
+    asm volatile("" : "+s"(u), "+v"(loff));
+#pragma unroll
+    for (int m = 0; m < NPF; ++m)
+      __builtin_amdgcn_global_load_lds((glb_void_t*)at(slot_ptr(u, m), loff), (lds_void_t*)(pf_l + (wv * NPF + m) * 128),
+                                       16, 0, (LD & F_NT_LD) ? 2 : 0);
+  }
+  // slot m < NPF, which the prefetch brought
+  template <int NPF>
+  __device__ __forceinline__ cd prefetched(int m, int lane) const {
+    return fromv(*reinterpret_cast<const dv2*>(pf_l + (wv * NPF + m) * 128 + 2 * lane));
+  }
+  template <int LD>
+  __device__ __forceinline__ cd load(int u, int m, unsigned loff) const {
+    return gload<LD>(at(slot_ptr(u, m), loff));
+  }
+  __device__ __forceinline__ void store(int u, int m, unsigned loff, cd v) const { gstore<0>(at(slot_ptr(u, m), loff), v); }
+};
+}  // namespace rec
+
 template <int PROBE, bool PF, int LD>
 __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPArgs& a, int nunits,
                                                 double* __restrict__ pf_l, cd* __restrict__ carr,
@@ -958,12 +1059,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
   const int wv = __builtin_amdgcn_readfirstlane(tid / 64);
   const i64 zs = (i64)TN << (a.lnyl ? a.lnyl : ilog2(TN));
   const cd lz = a.lamz;
-  // opaque copy of a lane index: what is derived from it is recomputed at its use instead of
-  // living in a register across the unit (k_tp_mid_sw's idx)
-  const auto idx = [](int i) {
-    asm volatile("" : "+v"(i));
-    return i;
-  };
+  using rec::pin, rec::cfma;
   // Column table of unit u: lane c = x + 8 y2 of wave 0 loads the symbol of column (x, brev3(y2)),
   // the column every wave's lane c scans after the y2 DFT, and
   // writes a = lamz / (c + lamz) and r = 256 / (c + lamz), one unit ahead (the unit's barrier
@@ -983,61 +1079,15 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
   if (tid < TN) tw_l[tid] = a.tw[tid];
   if (wv == 0 && (int)blockIdx.x < nunits) ctab_put(0, colsym_of((int)blockIdx.x));
   __syncthreads();
-  // a point's address = a wave-uniform base (unit u = (x tile, local k1): row 8 k1; slot m:
-  // z = 16 wv + m) + this lane's 32-bit byte offset (x, row y2): a scalar base plus one offset
-  // register for all 16 slots, instead of 16 address pairs
-  const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);
-  const auto slot_ptr = [&](int u, int m) {
-    return data + ((u % NXT) * XT + (i64)TN * N2 * (u / NXT) + zs * (16 * wv + m));
-  };
-  const auto at = [](cd* base, unsigned off) { return reinterpret_cast<cd*>(reinterpret_cast<char*>(base) + off); };
-  const auto prefetch = [&](int u) {  // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
-    unsigned lo0 = loff;
-    asm volatile("" : "+s"(u), "+v"(lo0));
-#pragma unroll
-    for (int m = 0; m < NPF; ++m)
-      __builtin_amdgcn_global_load_lds((glb_void_t*)at(slot_ptr(u, m), lo0), (lds_void_t*)(pf_l + (wv * NPF + m) * 128),
-                                       16, 0, (LD & F_NT_LD) ? 2 : 0);
-  };
+  const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);  // this lane's (x, row y2)
+  const rec::Tile tile{data, zs, wv, pf_l};
   if constexpr (PF) {
-    if ((int)blockIdx.x < nunits) prefetch((int)blockIdx.x);
+    if ((int)blockIdx.x < nunits) tile.prefetch<NPF, LD>((int)blockIdx.x, loff);
   }
   const cd zero = make_cd(0.0, 0.0);
-  // The y2 DFT's per-lane constants: the sign of the DPP stage (+1 where lane bit 3 is clear, -1
-  // where set) and the stage twiddles W_8^{y2 & 3} (lane bit 5) and W_4^{y2 & 1} (lane bit 4),
-  // which the two lanes of a pair share.
+  // the y2 DFT's per-lane constants (rec::y2_fwd_pair)
   const double s3 = (y2 & 1) ? -1.0 : 1.0;
   const cd w8 = a.tw[(TN / 8) * (y2 & 3)], w4 = a.tw[(TN / 4) * (y2 & 1)];
-  // Radix-2 stage over lane bit B (5 or 4) on the slot pair (p, q): the swap gives the lower lane
-  // both lanes' p and the upper lane both lanes' q, each lane runs one whole butterfly (no
-  // duplicated value, no half thrown away), and the second swap hands every lane its own results
-  // back: sums to the lower lane, differences to the upper.  DIF: a + b, (a - b) w.
-  const auto dif2 = [](auto bit, cd& p, cd& q, cd w) {
-    constexpr int B = decltype(bit)::value;
-    swap_c<B>(p, q);
-    const cd s = cadd(p, q), d = cmul(csub(p, q), w);
-    p = s;
-    q = d;
-    swap_c<B>(p, q);
-  };
-  // DIT: a + b w, a - b w
-  const auto dit2 = [](auto bit, cd& p, cd& q, cd w) {
-    constexpr int B = decltype(bit)::value;
-    swap_c<B>(p, q);
-    const cd t = cmul(q, w);
-    q = csub(p, t);
-    p = cadd(p, t);
-    swap_c<B>(p, q);
-  };
-  using bit5 = std::integral_constant<int, 5>;
-  using bit4 = std::integral_constant<int, 4>;
-  // pin(): the values are formed where the source forms them.  Sunk towards their uses, a DFT's
-  // or a column's last operations keep their inputs live as well and the kernel goes to scratch.
-  const auto pin = [](cd& w) { asm volatile("" : "+v"(w.x), "+v"(w.y)); };
-  // p q + c in 4 fused operations
-  const auto cfma = [](cd p, cd q, cd c) {
-    return make_cd(fma(p.x, q.x, fma(-p.y, q.y, c.x)), fma(p.x, q.y, fma(p.y, q.x, c.y)));
-  };
 
   // One unit.  MORE: another unit follows (its prefetch and column table are issued here); the
   // last unit is its own instantiation, so that every wait inside a unit knows what is in flight.
@@ -1046,8 +1096,13 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
     constexpr bool more = decltype(more_c)::value;
     const int u = it;
     const int k1 = a.k1_off + u / NXT;  // global k1
+    // (buf, then par, read here first: with par first read at its use below, the compiler orders
+    // the two loop counters the other way round and the kernel's scalar registers are renumbered)
     const int nbuf = buf == 2 ? 0 : buf + 1;
+    const int npar = par ^ 1;
     cd v[16], csn = zero;
+    // (the slot loops of the load and the store phase stay here and in tp_mid_rec2_body, one
+    // rec::Tile access per slot: moved whole into helpers that take v they spill, see rec)
     if constexpr (PROBE & PR_NO_LOAD) {
 #pragma unroll
       for (int m = 0; m < 16; ++m) v[m] = make_cd(lane + m, wv + u);
@@ -1057,8 +1112,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
         // behind a vmcnt(16) measured 0.7 % slower, profiles/r07_zrec_ab.txt)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int m = 0; m < NPF; ++m)
-          v[m] = fromv(*reinterpret_cast<const dv2*>(pf_l + (wv * NPF + m) * 128 + 2 * idx(lane)));
+        for (int m = 0; m < NPF; ++m) v[m] = tile.prefetched<NPF>(m, idx(lane));
       }
       if constexpr (more) csn = colsym_of(it + (int)gridDim.x);  // every wave loads (no wait at a join), wave 0 uses it
       {
@@ -1066,7 +1120,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
         unsigned lo1 = loff;
         asm volatile("" : "+s"(ul), "+v"(lo1));  // scalar base + this register, formed here
 #pragma unroll
-        for (int m = NPF; m < 16; ++m) v[m] = gload<LD>(at(slot_ptr(ul, m), lo1));
+        for (int m = NPF; m < 16; ++m) v[m] = tile.load<LD>(ul, m, lo1);
       }
     }
     if (more && wv == 0) ctab_put(nbuf, csn);
@@ -1082,12 +1136,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
     if constexpr (!(PROBE & PR_NO_Y2)) {
 #pragma unroll
       for (int m = 0; m < 16; m += 2) {
-        dif2(bit5{}, v[m], v[m + 1], w8);
-        dif2(bit4{}, v[m], v[m + 1], w4);
-        v[m] = bfly_l3(v[m], s3);
-        v[m + 1] = bfly_l3(v[m + 1], s3);
-        pin(v[m]);
-        pin(v[m + 1]);
+        rec::y2_fwd_pair(v[m], v[m + 1], w8, w4, s3);
         if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -1138,17 +1187,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
       const cd w = tw_l[((idx(lane) >> 3) * k1s) & (TN - 1)];
 #pragma unroll
       for (int m = 0; m < 16; m += 2) {
-        cd p = cconj(v[m]), q = cconj(v[m + 1]);
-        if constexpr (!(PROBE & PR_NO_Y2)) {
-          p = bfly_l3(p, s3);
-          q = bfly_l3(q, s3);
-          dit2(bit4{}, p, q, w4);
-          dit2(bit5{}, p, q, w8);
-        }
-        v[m] = cconj(cmul(p, w));
-        v[m + 1] = cconj(cmul(q, w));
-        pin(v[m]);
-        pin(v[m + 1]);
+        rec::y2_inv_pair<PROBE>(v[m], v[m + 1], w, w8, w4, s3);
         if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
       }
       // The next unit's prefetch goes out here, behind all of this unit's arithmetic and in
@@ -1157,21 +1196,21 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
       // 90.0 us instead of 86.0 (profiles/r08_zrows_probe.txt).  No global load follows it inside
       // the unit, so no wait drains it early.
       if constexpr (PF && more && !(PROBE & PR_NO_LOAD)) {
-        prefetch(it + (int)gridDim.x);
+        tile.prefetch<NPF, LD>(it + (int)gridDim.x, loff);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (!(PROBE & PR_NO_STORE)) {
 #pragma unroll
-        for (int m = 0; m < 16; ++m) gstore<0>(at(slot_ptr(us, m), lo2), v[m]);
+        for (int m = 0; m < 16; ++m) tile.store(us, m, lo2, v[m]);
       }
       if constexpr (PROBE & PR_NO_STORE) {
         double acc = 0.0;
 #pragma unroll
         for (int m = 0; m < 16; ++m) acc += v[m].x + v[m].y;
-        if (acc == 1.2345e300) *at(slot_ptr(us, 0), lo2) = make_cd(acc, 0.0);  // keeps the work live, never true
+        if (acc == 1.2345e300) tile.store(us, 0, lo2, make_cd(acc, 0.0));  // keeps the work live, never true
       }
     }
-    par ^= 1;
+    par = npar;
     buf = nbuf;
   };
   int it = blockIdx.x;
@@ -1222,18 +1261,13 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
                                                  double* __restrict__ pf_l, cd* __restrict__ carr,
                                                  cd* __restrict__ ctab, cd* __restrict__ tw_l,
                                                  const cd* __restrict__ tab2) {
-  constexpr int TN = 256, N2 = 8, XT = 8, NXT = TN / XT, NW = 16;
+  constexpr int TN = 256, NXT = rec::Tile::NXT, NW = 16;
   constexpr int NPF = PF ? kRecNPF : 0;
   const int tid = threadIdx.x;
   const int lane = tid & 63, x = lane & 7, y2 = lane >> 3;
   const int wv = __builtin_amdgcn_readfirstlane(tid / 64);
   const i64 zs = (i64)TN << (a.lnyl ? a.lnyl : ilog2(TN));
-  // (idx, at, slot_ptr, prefetch, dif2, dit2, pin, cfma: as in tp_mid_rec_body)
-  const auto idx = [](int i) {
-    asm volatile("" : "+v"(i));
-    return i;
-  };
-  const auto at = [](cd* base, unsigned off) { return reinterpret_cast<cd*>(reinterpret_cast<char*>(base) + off); };
+  using rec::at, rec::pin, rec::cfma;
   // unit u's a, r, b of the host's table -> ctab[buf] by LDS-DMA, lane-linear (wave 0)
   const auto tab_fetch = [&](int u, int buf) {
     unsigned lo = 16u * (unsigned)lane;
@@ -1250,45 +1284,14 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
-  const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);
-  const auto slot_ptr = [&](int u, int m) {
-    return data + ((u % NXT) * XT + (i64)TN * N2 * (u / NXT) + zs * (16 * wv + m));
-  };
-  const auto prefetch = [&](int u) {  // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
-    unsigned lo0 = loff;
-    asm volatile("" : "+s"(u), "+v"(lo0));
-#pragma unroll
-    for (int m = 0; m < NPF; ++m)
-      __builtin_amdgcn_global_load_lds((glb_void_t*)at(slot_ptr(u, m), lo0), (lds_void_t*)(pf_l + (wv * NPF + m) * 128),
-                                       16, 0, (LD & F_NT_LD) ? 2 : 0);
-  };
+  const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);  // this lane's (x, row y2)
+  const rec::Tile tile{data, zs, wv, pf_l};
   if constexpr (PF) {
-    if ((int)blockIdx.x < nunits) prefetch((int)blockIdx.x);
+    if ((int)blockIdx.x < nunits) tile.prefetch<NPF, LD>((int)blockIdx.x, loff);
   }
+  // the y2 DFT's per-lane constants (rec::y2_fwd_pair)
   const double s3 = (y2 & 1) ? -1.0 : 1.0;
   const cd w8 = a.tw[(TN / 8) * (y2 & 3)], w4 = a.tw[(TN / 4) * (y2 & 1)];
-  const auto dif2 = [](auto bit, cd& p, cd& q, cd w) {
-    constexpr int B = decltype(bit)::value;
-    swap_c<B>(p, q);
-    const cd s = cadd(p, q), d = cmul(csub(p, q), w);
-    p = s;
-    q = d;
-    swap_c<B>(p, q);
-  };
-  const auto dit2 = [](auto bit, cd& p, cd& q, cd w) {
-    constexpr int B = decltype(bit)::value;
-    swap_c<B>(p, q);
-    const cd t = cmul(q, w);
-    q = csub(p, t);
-    p = cadd(p, t);
-    swap_c<B>(p, q);
-  };
-  using bit5 = std::integral_constant<int, 5>;
-  using bit4 = std::integral_constant<int, 4>;
-  const auto pin = [](cd& w) { asm volatile("" : "+v"(w.x), "+v"(w.y)); };
-  const auto cfma = [](cd p, cd q, cd c) {
-    return make_cd(fma(p.x, q.x, fma(-p.y, q.y, c.x)), fma(p.x, q.y, fma(p.y, q.x, c.y)));
-  };
   // the cyclic closure of a Horner sum: acc / (1 - P16^16), P16 the ratio's 16th power
   const auto close = [](cd acc, cd P16) {
     const cd P2 = cmul(P16, P16), P4 = cmul(P2, P2), P8 = cmul(P4, P4), P = cmul(P8, P8);
@@ -1316,15 +1319,14 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
       if constexpr (PF) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA landed
 #pragma unroll
-        for (int m = 0; m < NPF; ++m)
-          v[m] = fromv(*reinterpret_cast<const dv2*>(pf_l + (wv * NPF + m) * 128 + 2 * idx(lane)));
+        for (int m = 0; m < NPF; ++m) v[m] = tile.prefetched<NPF>(m, idx(lane));
       }
       {
         int ul = u;
         unsigned lo1 = loff;
         asm volatile("" : "+s"(ul), "+v"(lo1));  // scalar base + this register, formed here
 #pragma unroll
-        for (int m = NPF; m < 16; ++m) v[m] = gload<LD>(at(slot_ptr(ul, m), lo1));
+        for (int m = NPF; m < 16; ++m) v[m] = tile.load<LD>(ul, m, lo1);
       }
     }
     // twiddle W_256^{y2 k1}
@@ -1338,12 +1340,7 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
     if constexpr (!(PROBE & PR_NO_Y2)) {
 #pragma unroll
       for (int m = 0; m < 16; m += 2) {
-        dif2(bit5{}, v[m], v[m + 1], w8);
-        dif2(bit4{}, v[m], v[m + 1], w4);
-        v[m] = bfly_l3(v[m], s3);
-        v[m + 1] = bfly_l3(v[m + 1], s3);
-        pin(v[m]);
-        pin(v[m + 1]);
+        rec::y2_fwd_pair(v[m], v[m + 1], w8, w4, s3);
         if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -1407,36 +1404,26 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
       const cd w = tw_l[((idx(lane) >> 3) * k1s) & (TN - 1)];
 #pragma unroll
       for (int m = 0; m < 16; m += 2) {
-        cd p = cconj(v[m]), q = cconj(v[m + 1]);
-        if constexpr (!(PROBE & PR_NO_Y2)) {
-          p = bfly_l3(p, s3);
-          q = bfly_l3(q, s3);
-          dit2(bit4{}, p, q, w4);
-          dit2(bit5{}, p, q, w8);
-        }
-        v[m] = cconj(cmul(p, w));
-        v[m + 1] = cconj(cmul(q, w));
-        pin(v[m]);
-        pin(v[m + 1]);
+        rec::y2_inv_pair<PROBE>(v[m], v[m + 1], w, w8, w4, s3);
         if ((m & 2) == 2) __builtin_amdgcn_sched_barrier(0);
       }
       // behind all of this unit's arithmetic and in front of its stores: the next unit's prefetch
       // and the table of the unit after it (nobody reads that buffer any more: its last readers
       // passed this unit's second barrier)
       if constexpr (more) {
-        if constexpr (PF && !(PROBE & PR_NO_LOAD)) prefetch(it + (int)gridDim.x);
+        if constexpr (PF && !(PROBE & PR_NO_LOAD)) tile.prefetch<NPF, LD>(it + (int)gridDim.x, loff);
         if (wv == 0 && it + 2 * (int)gridDim.x < nunits) tab_fetch(it + 2 * (int)gridDim.x, nbuf == 2 ? 0 : nbuf + 1);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (!(PROBE & PR_NO_STORE)) {
 #pragma unroll
-        for (int m = 0; m < 16; ++m) gstore<0>(at(slot_ptr(us, m), lo2), v[m]);
+        for (int m = 0; m < 16; ++m) tile.store(us, m, lo2, v[m]);
       }
       if constexpr (PROBE & PR_NO_STORE) {
         double acc = 0.0;
 #pragma unroll
         for (int m = 0; m < 16; ++m) acc += v[m].x + v[m].y;
-        if (acc == 1.2345e300) *at(slot_ptr(us, 0), lo2) = make_cd(acc, 0.0);  // keeps the work live, never true
+        if (acc == 1.2345e300) tile.store(us, 0, lo2, make_cd(acc, 0.0));  // keeps the work live, never true
       }
     }
     buf = nbuf;
@@ -1546,10 +1533,6 @@ k_tp_rows_r2c(const double* in_r, cd* H, cd* Q, double* out_r, TPArgs a, int nun
   const int r0 = tid / TPC, tpc0 = tid % TPC;  // row mode: row r (= y1), thread tpc
   // column mode: column kx, thread ty
   const int x0 = WL ? (tid >> 6) * 16 + (tid & 15) : tid % M, ty0 = WL ? (tid >> 4) & 3 : tid / M;
-  const auto idx = [](int i) {
-    asm volatile("" : "+v"(i));
-    return i;
-  };
   // row mode (row r, Z[k], k = tpc + TPC t) -> column mode (column kx, rows ty + TY m), with the
   // r2c even/odd split done on the way: each thread also reads its mirror bin Z[M - kx] of the
   // same rows from the transpose buffer (no cross-lane shuffles)

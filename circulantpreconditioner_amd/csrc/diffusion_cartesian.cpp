@@ -21,11 +21,11 @@
 #include "../../include/diffusion_equation.h"
 #include "../../include/pcshell_fft3d.h"
 #include "../../include/transport_equation.h"
-#include "gmres_time_loop.h"
+#include "cartesian_driver.h"
 #include "pcshell_common.h"
 
 using namespace cfp_pc;
-using cfp_loop::wall;
+using cfp_driver::wall;
 
 static_assert(offsetof(FFTPrecDiffusionContext, b_cartesien) == offsetof(FFTPrecTransportContext, b_cartesien) &&
                   offsetof(FFTPrecDiffusionContext, lambda_z) == offsetof(FFTPrecTransportContext, lambda_z) &&
@@ -128,8 +128,6 @@ int advdiff_csr_rows(int64_t nx, int64_t ny, int64_t nz, const double h[3], doub
   *nnz = p;
   return CFP_SUCCESS;
 }
-
-double grid_h(const double xmin[3], const double xmax[3], int d, int64_t n) { return (xmax[d] - xmin[d]) / (double)n; }
 
 }  // namespace
 
@@ -246,22 +244,13 @@ extern "C" PetscErrorCode computeAdvectionDiffusionMatrixCartesianAIJ(MPI_Comm c
     PetscCall(MatCreateSeqAIJWithArrays(comm, N, N, rowptr.data(), col.data(), val.data(), A));
     PetscFunctionReturn(PETSC_SUCCESS);
   }
-  PetscCall(MatCreateAIJ(comm, PETSC_DECIDE, PETSC_DECIDE, N, N, 7, NULL, 6, NULL, A));
-  PetscInt lo, hi;
-  PetscCall(MatGetOwnershipRange(*A, &lo, &hi));
-  const int64_t m = hi - lo;
-  std::vector<int64_t> rowptr((size_t)m + 1), col((size_t)(7 * (m > 0 ? m : 1)));
-  std::vector<PetscScalar> val((size_t)(7 * (m > 0 ? m : 1)));
-  int64_t nnz = 0;
-  const int rc = advdiff_csr_rows(nx, ny, nz, h, dt, a, nu, (int)bc, 0.0, lo, hi, rowptr.data(), col.data(),
-                                  reinterpret_cast<double*>(val.data()), &nnz);
-  PetscCheck(rc == CFP_SUCCESS, PETSC_COMM_SELF, rc, "computeAdvectionDiffusionMatrixCartesianAIJ: bad arguments");
-  for (int64_t r = 0; r < m; ++r) {
-    const PetscInt row = lo + r, k = rowptr[(size_t)r + 1] - rowptr[(size_t)r];
-    PetscCall(MatSetValues(*A, 1, &row, k, col.data() + rowptr[(size_t)r], val.data() + rowptr[(size_t)r], ADD_VALUES));
-  }
-  PetscCall(MatAssemblyBegin(*A, MAT_FINAL_ASSEMBLY));
-  PetscCall(MatAssemblyEnd(*A, MAT_FINAL_ASSEMBLY));
+  const auto rows = [&](int64_t lo, int64_t hi, int64_t* rowptr, int64_t* col, double* val,
+                        int64_t* nnz) -> PetscErrorCode {
+    const int rc = advdiff_csr_rows(nx, ny, nz, h, dt, a, nu, (int)bc, 0.0, lo, hi, rowptr, col, val, nnz);
+    PetscCheck(rc == CFP_SUCCESS, PETSC_COMM_SELF, rc, "computeAdvectionDiffusionMatrixCartesianAIJ: bad arguments");
+    return PETSC_SUCCESS;
+  };
+  PetscCall(cfp_driver::aij_from_rows(comm, N, rows, A));
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 
@@ -304,16 +293,13 @@ extern "C" PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config* cfg,
   const PetscInt nx = cfg->nx, ny = cfg->ny, nz = cfg->nz, N = nx * ny * nz;
   PetscCheck(nx >= 1 && ny >= 1 && nz >= 1, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
   const int dim = nz > 1 ? 3 : (ny > 1 ? 2 : 1);
-  const double h[3] = {grid_h(cfg->xmin, cfg->xmax, 0, nx), grid_h(cfg->xmin, cfg->xmax, 1, ny),
-                       grid_h(cfg->xmin, cfg->xmax, 2, nz)};
+  double h[3];
+  cfp_driver::grid_spacing(cfg, h);
   const double dt = cfg->dt;
   res->dt = dt;
 
   Vec Un, dUn;
-  if (cfg->on_device) PetscCall(VecCreateSeqHIP(PETSC_COMM_SELF, N, &Un));
-  else PetscCall(VecCreateSeq(PETSC_COMM_SELF, N, &Un));
-  PetscCall(VecDuplicate(Un, &dUn));
-  PetscCall(initial_conditions_shock_cartesian(nx, ny, nz, cfg->xmin, cfg->xmax, Un));
+  PetscCall(cfp_driver::create_state(cfg, 1, &Un, &dUn));
 
   Mat A;
   PetscCall(computeAdvectionDiffusionMatrixCartesianAIJ(PETSC_COMM_SELF, nx, ny, nz, h, dt, cfg->a, cfg->nu, cfg->bc, &A));
@@ -321,14 +307,8 @@ extern "C" PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config* cfg,
 
   KSP ksp;
   PC pc;
-  PetscCall(KSPCreate(PETSC_COMM_WORLD, &ksp));
-  PetscCall(KSPSetType(ksp, KSPGMRES));
-  PetscCall(KSPSetTolerances(ksp, cfg->precision, cfg->precision, PETSC_DEFAULT, cfg->max_its));
-  PetscCall(KSPGMRESSetRestart(ksp, cfg->restart > 0 ? cfg->restart : 30));
-  PetscCall(KSPSetPCSide(ksp, (PCSide)cfg->pc_side));
   // the 7-point stencil is not x-local: MatMult, PCApply and the dots run as separate sweeps
-  PetscCall(KSPMiniSetFusion(ksp, PETSC_FALSE));
-  PetscCall(KSPGetPC(ksp, &pc));
+  PetscCall(cfp_driver::gmres_create(cfg, PETSC_FALSE, &ksp, &pc));
   FFTPrecDiffusionContext ctx;
   std::memset((void*)&ctx, 0, sizeof(ctx));
   if (cfg->pc == CFP_ADVDIFF_PC_FFT) {
@@ -349,22 +329,10 @@ extern "C" PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config* cfg,
   } else {
     PetscCall(PCSetType(pc, PCNONE));
   }
-  PetscCall(KSPSetOperators(ksp, A, A));
-  PetscCall(KSPSetUp(ksp));
-  // the Krylov basis and the device copy of A now, outside the timed solves
-  PetscCall(KSPMiniSetUpWork(ksp, Un));
-  PetscCall(MatMult(A, Un, dUn));
-  if (cfg->on_device)
-    PetscCheck(cfp_stream_sync(nullptr) == CFP_SUCCESS, PETSC_COMM_SELF, PETSC_ERR_LIB, "stream sync failed");
-  res->setup_seconds = wall() - t_setup;
+  PetscCall(cfp_driver::gmres_setup(ksp, A, Un, dUn, cfg->on_device, t_setup, res));
 
-  PetscCall(cfp_loop::gmres_time_loop(ksp, Un, dUn, dt, cfg->ntmax, cfg->tmax, cfg->precision, cfg->profile, res));
-  if (U_out) {
-    const PetscScalar* u;
-    PetscCall(VecGetArrayRead(Un, &u));
-    std::memcpy(U_out, (const void*)u, sizeof(double) * 2 * (size_t)N);
-    PetscCall(VecRestoreArrayRead(Un, &u));
-  }
+  PetscCall(cfp_driver::gmres_time_loop(ksp, Un, dUn, dt, cfg, res));
+  PetscCall(cfp_driver::copy_out(Un, N, U_out));
   PetscCall(KSPDestroy(&ksp));  // destroys the PC, whose destroy callback frees setup's objects
   PetscCall(MatDestroy(&A));
   PetscCall(VecDestroy(&Un));
@@ -381,8 +349,8 @@ extern "C" PetscErrorCode AdvectionDiffusionFFTDirect(const cfp_advdiff_config* 
   const double t_setup = wall();
   const PetscInt nx = cfg->nx, ny = cfg->ny, nz = cfg->nz, N = nx * ny * nz;
   PetscCheck(nx >= 1 && ny >= 1 && nz >= 1, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
-  const double h[3] = {grid_h(cfg->xmin, cfg->xmax, 0, nx), grid_h(cfg->xmin, cfg->xmax, 1, ny),
-                       grid_h(cfg->xmin, cfg->xmax, 2, nz)};
+  double h[3];
+  cfp_driver::grid_spacing(cfg, h);
   const double dt = cfg->dt;
   res->dt = dt;
   const PetscInt n[3] = {nx, ny, nz};
@@ -392,10 +360,7 @@ extern "C" PetscErrorCode AdvectionDiffusionFFTDirect(const cfp_advdiff_config* 
     res->mu[d] = n[d] > 1 ? cfg->nu * dt / (h[d] * h[d]) : 0.0;
   }
   Vec Un, dUn;
-  if (cfg->on_device) PetscCall(VecCreateSeqHIP(PETSC_COMM_SELF, N, &Un));
-  else PetscCall(VecCreateSeq(PETSC_COMM_SELF, N, &Un));
-  PetscCall(VecDuplicate(Un, &dUn));
-  PetscCall(initial_conditions_shock_cartesian(nx, ny, nz, cfg->xmin, cfg->xmax, Un));
+  PetscCall(cfp_driver::create_state(cfg, 1, &Un, &dUn));
   Mat FFT_MAT;
   const PetscInt dims[3] = {nz, ny, nx};
   PetscCall(MatCreateFFT(PETSC_COMM_WORLD, 3, dims, MATFFTW, &FFT_MAT));
@@ -403,35 +368,9 @@ extern "C" PetscErrorCode AdvectionDiffusionFFTDirect(const cfp_advdiff_config* 
                                            FFT_MAT};
   res->setup_seconds = wall() - t_setup;
 
-  int64_t it = 0;
-  double time = 0.0;
-  bool stationary = false;
-  res->all_converged = 1;
-  while (it < cfg->ntmax && time <= cfg->tmax && !stationary) {
-    PetscCall(VecCopy(Un, dUn));
-    PetscCall(VecMiniSynchronize(dUn));  // the clock brackets the solve only (TransportEquationFFTDirect)
-    const double v = wall();
-    PetscCall(PetscFft3DDiffusionSolver(ctx, Un, Un));
-    PetscCall(VecMiniSynchronize(Un));
-    const double w = wall();
-    PetscCall(VecAXPY(dUn, -1.0, Un));
-    time += dt;
-    it += 1;
-    PetscReal norm;
-    PetscCall(VecNorm(dUn, NORM_2, &norm));
-    stationary = norm < cfg->precision;
-    res->solve_seconds += w - v;
-    res->pc_calls += 1;
-    res->last_norm_dU = norm;
-  }
-  res->steps = it;
-  res->time = time;
-  if (U_out) {
-    const PetscScalar* u;
-    PetscCall(VecGetArrayRead(Un, &u));
-    std::memcpy(U_out, (const void*)u, sizeof(double) * 2 * (size_t)N);
-    PetscCall(VecRestoreArrayRead(Un, &u));
-  }
+  const auto solve = [&](Vec U) { return PetscFft3DDiffusionSolver(ctx, U, U); };
+  PetscCall(cfp_driver::direct_time_loop(Un, dUn, dt, cfg, solve, res));
+  PetscCall(cfp_driver::copy_out(Un, N, U_out));
   PetscCall(MatDestroy(&FFT_MAT));
   PetscCall(VecDestroy(&Un));
   PetscCall(VecDestroy(&dUn));

@@ -21,9 +21,9 @@
 #include "../../include/circulant_fft.h"
 #include "../../include/pcshell_fft3d.h"
 #include "../../include/transport_equation.h"
-#include "gmres_time_loop.h"
+#include "cartesian_driver.h"
 
-using cfp_loop::wall;
+using cfp_driver::wall;
 
 // One row per cell; the six faces of cell (i,j,k) in the order -x,+x,-y,+y,-z,+z with outward
 // normals; un = n . a.  Interior face: un > 0 adds dt |F|/|C| un to the diagonal (:109-110);
@@ -130,23 +130,13 @@ extern "C" PetscErrorCode computeDivergenceMatrixCartesianAIJ(MPI_Comm comm, Pet
   PetscFunctionBeginUser;
   PetscCheck(A && h && a, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "computeDivergenceMatrixCartesianAIJ: NULL argument");
   PetscCheck(nx >= 1 && ny >= 1 && nz >= 1, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
-  const int64_t N = nx * ny * nz;
-  PetscCall(MatCreateAIJ(comm, PETSC_DECIDE, PETSC_DECIDE, N, N, 7, NULL, 6, NULL, A));
-  PetscInt lo, hi;
-  PetscCall(MatGetOwnershipRange(*A, &lo, &hi));
-  const int64_t m = hi - lo;
-  std::vector<int64_t> rowptr((size_t)m + 1), col((size_t)(7 * (m > 0 ? m : 1)));
-  std::vector<PetscScalar> val((size_t)(7 * (m > 0 ? m : 1)));
-  int64_t nnz = 0;
-  const int rc = transport_csr_rows(nx, ny, nz, h, dt, a, (int)sign_mode, 0.0, lo, hi, rowptr.data(), col.data(),
-                                    reinterpret_cast<double*>(val.data()), &nnz);
-  PetscCheck(rc == CFP_SUCCESS, PETSC_COMM_SELF, rc, "computeDivergenceMatrixCartesianAIJ: bad arguments");
-  for (int64_t r = 0; r < m; ++r) {
-    const PetscInt row = lo + r, k = rowptr[(size_t)r + 1] - rowptr[(size_t)r];
-    PetscCall(MatSetValues(*A, 1, &row, k, col.data() + rowptr[(size_t)r], val.data() + rowptr[(size_t)r], ADD_VALUES));
-  }
-  PetscCall(MatAssemblyBegin(*A, MAT_FINAL_ASSEMBLY));
-  PetscCall(MatAssemblyEnd(*A, MAT_FINAL_ASSEMBLY));
+  const auto rows = [&](int64_t lo, int64_t hi, int64_t* rowptr, int64_t* col, double* val,
+                        int64_t* nnz) -> PetscErrorCode {
+    const int rc = transport_csr_rows(nx, ny, nz, h, dt, a, (int)sign_mode, 0.0, lo, hi, rowptr, col, val, nnz);
+    PetscCheck(rc == CFP_SUCCESS, PETSC_COMM_SELF, rc, "computeDivergenceMatrixCartesianAIJ: bad arguments");
+    return PETSC_SUCCESS;
+  };
+  PetscCall(cfp_driver::aij_from_rows(comm, nx * ny * nz, rows, A));
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 
@@ -213,8 +203,8 @@ extern "C" PetscErrorCode TransportEquationGMRES(const cfp_transport_config* cfg
   const double t_setup = wall();
   const PetscInt nx = cfg->nx, ny = cfg->ny, nz = cfg->nz, N = nx * ny * nz;
   const int dim = nz > 1 ? 3 : (ny > 1 ? 2 : 1);
-  const double h[3] = {(cfg->xmax[0] - cfg->xmin[0]) / (double)nx, (cfg->xmax[1] - cfg->xmin[1]) / (double)ny,
-                       (cfg->xmax[2] - cfg->xmin[2]) / (double)nz};
+  double h[3];
+  cfp_driver::grid_spacing(cfg, h);
   const double anorm = std::sqrt(cfg->a[0] * cfg->a[0] + cfg->a[1] * cfg->a[1] + cfg->a[2] * cfg->a[2]);
   PetscCheck(anorm > 0, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, "transport velocity is zero");
   const double dt = cfg->cfl * cfp_cartesian_min_ratio_vol_surf(dim, h) / anorm;  // :54
@@ -225,12 +215,7 @@ extern "C" PetscErrorCode TransportEquationGMRES(const cfp_transport_config* cfg
   int P = 1;
   PetscCallMPI(MPI_Comm_size(PETSC_COMM_WORLD, &P));
   Vec Un, dUn;
-  if (P > 1 && cfg->on_device) PetscCall(VecCreateMPIHIP(PETSC_COMM_WORLD, PETSC_DECIDE, N, &Un));
-  else if (P > 1) PetscCall(VecCreateMPI(PETSC_COMM_WORLD, PETSC_DECIDE, N, &Un));
-  else if (cfg->on_device) PetscCall(VecCreateSeqHIP(PETSC_COMM_SELF, N, &Un));
-  else PetscCall(VecCreateSeq(PETSC_COMM_SELF, N, &Un));
-  PetscCall(VecDuplicate(Un, &dUn));
-  PetscCall(initial_conditions_shock_cartesian(nx, ny, nz, cfg->xmin, cfg->xmax, Un));
+  PetscCall(cfp_driver::create_state(cfg, P, &Un, &dUn));
   PetscInt lo, nloc;
   PetscCall(VecGetOwnershipRange(Un, &lo, NULL));
   PetscCall(VecGetLocalSize(Un, &nloc));
@@ -244,13 +229,7 @@ extern "C" PetscErrorCode TransportEquationGMRES(const cfp_transport_config* cfg
 
   KSP ksp;
   PC pc;
-  PetscCall(KSPCreate(PETSC_COMM_WORLD, &ksp));
-  PetscCall(KSPSetType(ksp, KSPGMRES));
-  PetscCall(KSPSetTolerances(ksp, cfg->precision, cfg->precision, PETSC_DEFAULT, cfg->max_its));
-  PetscCall(KSPGMRESSetRestart(ksp, cfg->restart > 0 ? cfg->restart : 30));
-  PetscCall(KSPSetPCSide(ksp, (PCSide)cfg->pc_side));
-  PetscCall(KSPMiniSetFusion(ksp, cfg->fuse ? PETSC_TRUE : PETSC_FALSE));
-  PetscCall(KSPGetPC(ksp, &pc));
+  PetscCall(cfp_driver::gmres_create(cfg, cfg->fuse ? PETSC_TRUE : PETSC_FALSE, &ksp, &pc));
   FFTPrecTransportContext ctx;
   std::memset((void*)&ctx, 0, sizeof(ctx));
   if (cfg->pc == CFP_TRANSPORT_PC_FFT) {
@@ -279,24 +258,10 @@ extern "C" PetscErrorCode TransportEquationGMRES(const cfp_transport_config* cfg
   } else {
     PetscCall(PCSetType(pc, PCNONE));
   }
-  PetscCall(KSPSetOperators(ksp, A, A));
-  PetscCall(KSPSetUp(ksp));
-  // allocate the Krylov basis and make the device copy of A now, so the timed solves hold
-  // only the solver's own work (PETSc would do both inside the first KSPSolve)
-  PetscCall(KSPMiniSetUpWork(ksp, Un));
-  PetscCall(MatMult(A, Un, dUn));
-  if (cfg->on_device)
-    PetscCheck(cfp_stream_sync(nullptr) == CFP_SUCCESS, PETSC_COMM_SELF, PETSC_ERR_LIB, "stream sync failed");
-  res->setup_seconds = wall() - t_setup;
+  PetscCall(cfp_driver::gmres_setup(ksp, A, Un, dUn, cfg->on_device, t_setup, res));
 
-  // the time loop (:131-170), shared with AdvectionDiffusionGMRES
-  PetscCall(cfp_loop::gmres_time_loop(ksp, Un, dUn, dt, cfg->ntmax, cfg->tmax, cfg->precision, cfg->profile, res));
-  if (U_out) {  // this rank's rows (all of them on one rank)
-    const PetscScalar* u;
-    PetscCall(VecGetArrayRead(Un, &u));
-    std::memcpy(U_out, (const void*)u, sizeof(double) * 2 * (size_t)nloc);
-    PetscCall(VecRestoreArrayRead(Un, &u));
-  }
+  PetscCall(cfp_driver::gmres_time_loop(ksp, Un, dUn, dt, cfg, res));  // :131-170
+  PetscCall(cfp_driver::copy_out(Un, nloc, U_out));
   PetscCall(KSPDestroy(&ksp));  // destroys the PC, whose destroy callback frees setup's objects
   PetscCall(MatDestroy(&A));
   PetscCall(VecDestroy(&Un));
@@ -315,8 +280,8 @@ extern "C" PetscErrorCode TransportEquationFFTDirect(const cfp_transport_config*
   const PetscInt nx = cfg->nx, ny = cfg->ny, nz = cfg->nz, N = nx * ny * nz;
   PetscCheck(nx >= 1 && ny >= 1 && nz >= 1, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
   const int dim = nz > 1 ? 3 : (ny > 1 ? 2 : 1);
-  const double h[3] = {(cfg->xmax[0] - cfg->xmin[0]) / (double)nx, (cfg->xmax[1] - cfg->xmin[1]) / (double)ny,
-                       (cfg->xmax[2] - cfg->xmin[2]) / (double)nz};
+  double h[3];
+  cfp_driver::grid_spacing(cfg, h);
   // the velocity has dim components in the reference (Vector(getSpaceDimension())): the others are 0
   const double a[3] = {cfg->a[0], dim > 1 ? cfg->a[1] : 0.0, dim > 2 ? cfg->a[2] : 0.0};
   const double anorm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
@@ -326,10 +291,7 @@ extern "C" PetscErrorCode TransportEquationFFTDirect(const cfp_transport_config*
   for (int d = 0; d < 3; ++d) res->lambda[d] = a[d] * dt / h[d];
 
   Vec Un, dUn;
-  if (cfg->on_device) PetscCall(VecCreateSeqHIP(PETSC_COMM_SELF, N, &Un));
-  else PetscCall(VecCreateSeq(PETSC_COMM_SELF, N, &Un));
-  PetscCall(VecDuplicate(Un, &dUn));
-  PetscCall(initial_conditions_shock_cartesian(nx, ny, nz, cfg->xmin, cfg->xmax, Un));
+  PetscCall(cfp_driver::create_state(cfg, 1, &Un, &dUn));
 
   Mat FFT_MAT;
   const PetscInt dims[3] = {nz, ny, nx};
@@ -337,37 +299,9 @@ extern "C" PetscErrorCode TransportEquationFFTDirect(const cfp_transport_config*
   struct StructuredTransportContext ctx = {nx, ny, nz, a[0], a[1], a[2], dt, h[0], h[1], h[2], FFT_MAT};  // :100
   res->setup_seconds = wall() - t_setup;
 
-  int64_t it = 0;
-  double time = 0.0;
-  bool stationary = false;
-  res->all_converged = 1;
-  while (it < cfg->ntmax && time <= cfg->tmax && !stationary) {  // :106
-    PetscCall(VecCopy(Un, dUn));
-    // the copy above is queued on the Vec stream (PETSc's host VecCopy returns when done): drain
-    // it, so that the clock brackets the solve only, as the reference's PetscTime pair (:110-112)
-    PetscCall(VecMiniSynchronize(dUn));
-    const double v = wall();
-    PetscCall(PetscFft3DTransportSolver(ctx, Un, Un));  // :111
-    PetscCall(VecMiniSynchronize(Un));  // a device-Vec solve is stream-ordered: time it to completion
-    const double w = wall();
-    PetscCall(VecAXPY(dUn, -1.0, Un));
-    time += dt;
-    it += 1;
-    PetscReal norm;
-    PetscCall(VecNorm(dUn, NORM_2, &norm));
-    stationary = norm < cfg->precision;
-    res->solve_seconds += w - v;
-    res->pc_calls += 1;
-    res->last_norm_dU = norm;
-  }
-  res->steps = it;
-  res->time = time;
-  if (U_out) {
-    const PetscScalar* u;
-    PetscCall(VecGetArrayRead(Un, &u));
-    std::memcpy(U_out, (const void*)u, sizeof(double) * 2 * (size_t)N);
-    PetscCall(VecRestoreArrayRead(Un, &u));
-  }
+  const auto solve = [&](Vec U) { return PetscFft3DTransportSolver(ctx, U, U); };
+  PetscCall(cfp_driver::direct_time_loop(Un, dUn, dt, cfg, solve, res));
+  PetscCall(cfp_driver::copy_out(Un, N, U_out));
   PetscCall(MatDestroy(&FFT_MAT));
   PetscCall(VecDestroy(&Un));
   PetscCall(VecDestroy(&dUn));
