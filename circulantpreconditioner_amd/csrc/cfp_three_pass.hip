@@ -148,13 +148,72 @@ enum { PR_NO_Y2 = 1, PR_NO_ZMATH = 2, PR_NO_XCHG = 4, PR_NO_LOAD = 8, PR_NO_STOR
 // a.post_nv <= NP; a NULL vector is x itself) across all its units and writes one partial per
 // workgroup and value: the VecMDot that follows a PCApply in classical Gram-Schmidt, without the
 // separate sweep that re-reads x.
+//
+// PF = NPF > 0 (the one-GPU 256^3 sweeps: N1 = 32, lane pairs, wave-local phase C, natural layout,
+// whole rounds, `in` 16-byte aligned): slots 0 .. NPF-1 of the workgroup's next unit come by
+// LDS-DMA (global_load_lds_dwordx4, lane-linear) into the issuing wave's own four rows of the
+// exchange buffer, which only that wave touches from the last transpose barrier to the next
+// unit's transpose.  The DMA goes out behind the unit's last arithmetic and in front of its
+// stores (one burst); the next unit loads slots NPF .. 15 from global memory, waits once for
+// everything and reads its own 16 bytes per slot back.  The barrier that closed the unit moves in
+// front of the transpose's first write, behind every wave's read of its prefetched slots: the
+// same number of barriers.  A workgroup's last unit prefetches nothing.
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) void glb_void_t;
+namespace rows {
+// A unit's loads in the natural one-GPU layout.  A point's address = a wave-uniform base (unit
+// u = (z, y2), the wave's 32 columns, slot m: rows 16 m further) + this lane's 32-bit byte offset
+// (x % 32, ty): a scalar base plus one offset register for all 16 slots (as rec::Tile below)
+struct Tile {
+  static constexpr int TN = 256, N2 = 8;
+  const cd* in;
+  int wv;
+  double* pf_l;  // this wave's rows of the exchange buffer
+  // the lane's column x (its low 5 bits: the lane's place in the wave's 32 columns) and its ty
+  static __device__ __forceinline__ unsigned lane_off(int x, int ty) {
+    return 16u * ((unsigned)(x & 31) + (unsigned)(TN * N2) * (unsigned)ty);
+  }
+  static __device__ __forceinline__ const cd* at(const cd* base, unsigned off) {
+    return reinterpret_cast<const cd*>(reinterpret_cast<const char*>(base) + off);
+  }
+  __device__ __forceinline__ const cd* slot_ptr(int u, int m) const {
+    // (an opaque scalar per slot: with the slot stride visible as a compile-time constant the
+    // lane's offset is added first and the 16 addresses become 64-bit vector additions)
+    i64 e = (i64)(u / N2) * TN * TN + (u % N2) * TN + 32 * wv + 2 * TN * N2 * m;
+    asm volatile("" : "+s"(e));
+    return in + e;
+  }
+  // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
+  template <int NPF, int LD>
+  __device__ __forceinline__ void prefetch(int u, unsigned loff) const {
+    asm volatile("" : "+s"(u), "+v"(loff));
+#pragma unroll
+    for (int m = 0; m < NPF; ++m)
+      __builtin_amdgcn_global_load_lds((glb_void_t*)at(slot_ptr(u, m), loff), (lds_void_t*)(pf_l + m * 128), 16, 0,
+                                       (LD & (F_NT | F_NT_LD)) ? 2 : 0);
+  }
+  // slot m < NPF, which the prefetch brought
+  __device__ __forceinline__ cd prefetched(int m, int lane) const {
+    return fromv(*reinterpret_cast<const dv2*>(pf_l + m * 128 + 2 * lane));
+  }
+  template <int LD>
+  __device__ __forceinline__ cd load(int u, int m, unsigned loff) const {
+    return gload<LD>(at(slot_ptr(u, m), loff));
+  }
+};
+}  // namespace rows
+
 template <bool INV, int FLAGS, int N1, int TN, int PTS = 16, bool XS = true, bool LP = false, int BLK = 0,
-          bool XCD = false, int PROBE = 0, int FUSE = 0>
+          bool XCD = false, int PROBE = 0, int FUSE = 0, int NPF = 0>
 __global__ void __launch_bounds__(N1 * (TN / PTS)) __attribute__((amdgpu_waves_per_eu(4)))
 k_tp_rows(const cd* in, cd* out, TPArgs a, int nunits) {
 #ifndef CFP_KEXP
   static_assert(PROBE == 0, "timing probes are built in tools/kexp only");
 #endif
+  constexpr bool PF = NPF > 0;
+  static_assert(!PF || (N1 == 32 && TN == 256 && PTS == 16 && XS && LP && BLK == 0 && FUSE == 0 &&
+                        (FLAGS & F_WAVE_LDS) != 0 && NPF <= 8),
+                "prefetch: the one-GPU 256^3 sweeps, at most 8 slots in the wave's own rows");
   constexpr int N2 = TN / N1, TR = TN / PTS, NT = N1 * TR, TY = N1 / PTS;
   constexpr bool PRE = !INV && FUSE == 1, POST = INV && FUSE > 0;
   constexpr int NP = POST ? FUSE : 1;
@@ -328,11 +387,43 @@ k_tp_rows(const cd* in, cd* out, TPArgs a, int nunits) {
     // (P3 100 -> 93 us at 256^3)
     __builtin_amdgcn_sched_barrier(0);
   };
+  // PF: the wave's four rows (rows 4 wv .. 4 wv + 3: its phase-C rows) take the prefetch
+  const auto pf_tile = [&]() {
+    const int wv = __builtin_amdgcn_readfirstlane(idx(x0) >> 5);  // x0 = lane % 32 + 32 wave
+    return rows::Tile{in, wv, lds + wv * (4 * RS)};
+  };
+  static_assert(!PF || (NPF * 128 <= 4 * RS && (4 * RS) % 2 == 0), "the prefetch fits the wave's rows, 16-byte aligned");
+  static_assert(!PF || !(PROBE & PR_ZMAJOR), "prefetch: blockIdx or XCD unit order");
+  if constexpr (PF && !(PROBE & PR_NO_LOAD)) {
+    if ((int)blockIdx.x < nunits)
+      pf_tile().template prefetch<NPF, FLAGS>(XCD ? xcd_unit(blockIdx.x, gridDim.x) : (int)blockIdx.x,
+                                              rows::Tile::lane_off(idx(x0), idx(ty0)));
+  }
   for (int it = blockIdx.x; it < nunits; it += gridDim.x) {
     int u = XCD ? xcd_unit(it, gridDim.x) : it;
     if constexpr ((PROBE & PR_ZMAJOR) != 0) u = (u % (nunits / N2)) * N2 + u / (nunits / N2);
     cd v[PTS];
-    load(u, v);
+    if constexpr (PF && !(PROBE & PR_NO_LOAD)) {
+      // slots NPF .. 15 from global memory first, then one wait for everything in flight: these
+      // loads, this wave's DMA and its stores of the previous unit
+      const rows::Tile tile = pf_tile();
+      {
+        int ul = u;
+        unsigned lo = rows::Tile::lane_off(idx(x0), idx(ty0));
+        asm volatile("" : "+s"(ul), "+v"(lo));  // scalar base + this register, formed here
+#pragma unroll
+        for (int m = NPF; m < PTS; ++m) v[m] = tile.template load<FLAGS>(ul, m, lo);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      {
+        const int lane = (idx(x0) & 31) + 32 * idx(ty0);
+#pragma unroll
+        for (int m = 0; m < NPF; ++m) v[m] = tile.prefetched(m, lane);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    } else {
+      load(u, v);
+    }
     if (INV) {
 #pragma unroll
       for (int m = 0; m < PTS; ++m) v[m] = cconj(v[m]);
@@ -364,6 +455,9 @@ k_tp_rows(const cd* in, cd* out, TPArgs a, int nunits) {
       fft_stages<N1, PTS, r0_of(N1, PTS), false, TN, FA>(v, lds, tw_l, x, ty, true);  // v[m]: k1 = ty + TY m
       lds_barrier();  // phase A's last LDS reads are done
     }
+    // PF: the unit's closing barrier stands here instead: every wave has read its prefetched slots
+    // (and finished the previous unit's phase C) before the transpose overwrites the rows
+    if constexpr (PF) lds_barrier();
     // phase B: transpose to rows k1, thread (row r, tx) gets x = tx + TR m
     if constexpr (!(PROBE & PR_NO_XCHG)) {
       const int x = idx(x0), ty = idx(ty0), r = idx(r0), tx = idx(tx0);
@@ -408,6 +502,11 @@ k_tp_rows(const cd* in, cd* out, TPArgs a, int nunits) {
 #pragma unroll
         for (int m = 0; m < PTS; ++m) acc += v[m].x * sc + v[m].y * sy;
         if (acc == 1.2345e300) out[tx] = make_cd(acc, 0.0);  // keeps the work live, never true
+        if constexpr (PF && !(PROBE & PR_NO_LOAD)) {
+          const int nx = it + (int)gridDim.x;
+          if (nx < nunits)
+            pf_tile().template prefetch<NPF, FLAGS>(XCD ? xcd_unit(nx, gridDim.x) : nx, rows::Tile::lane_off(idx(x0), idx(ty0)));
+        }
       } else if (BL && !INV) {  // blocked: kx = tx + TR m at (kx / BX) 64 + y2 BX + kx % BX of row block r
         cd* dst = out + crow(u / N2, N2 * r) + (u % N2) * BX + (tx / BX) * BW + tx % BX;
 #pragma unroll
@@ -415,10 +514,31 @@ k_tp_rows(const cd* in, cd* out, TPArgs a, int nunits) {
       } else {
         const i64 e0 = (INV ? (i64)(u / N2) * TN * TN + (i64)TN * (u % N2 + N2 * r) : crow(u / N2, u % N2 + N2 * r)) + tx;
         cd* dst = out + e0;
+        if constexpr (PF) {
+          // the next unit's prefetch goes out behind all of this unit's arithmetic and in front of
+          // its stores, which leave as one burst; no global load follows it inside the unit (a
+          // wait for one would wait for the DMA as well)
 #pragma unroll
-        for (int m = 0; m < PTS; ++m) {
-          v[m] = make_cd(v[m].x * sc, v[m].y * sy);
-          gstore<FLAGS>(dst + TR * m, v[m]);
+          for (int m = 0; m < PTS; ++m) v[m] = make_cd(v[m].x * sc, v[m].y * sy);
+          // (formed here: sunk below the branch round the prefetch, the row FFT's last stage
+          // would wait for its twiddle loads with the DMA in flight, and so for the DMA)
+#pragma unroll
+          for (int m = 0; m < PTS; ++m) asm volatile("" : "+v"(v[m].x), "+v"(v[m].y));
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (!(PROBE & PR_NO_LOAD)) {
+            const int nx = it + (int)gridDim.x;  // the last unit prefetches nothing
+            if (nx < nunits)
+              pf_tile().template prefetch<NPF, FLAGS>(XCD ? xcd_unit(nx, gridDim.x) : nx, rows::Tile::lane_off(idx(x0), idx(ty0)));
+            __builtin_amdgcn_sched_barrier(0);
+          }
+#pragma unroll
+          for (int m = 0; m < PTS; ++m) gstore<FLAGS>(dst + TR * m, v[m]);
+        } else {
+#pragma unroll
+          for (int m = 0; m < PTS; ++m) {
+            v[m] = make_cd(v[m].x * sc, v[m].y * sy);
+            gstore<FLAGS>(dst + TR * m, v[m]);
+          }
         }
         if constexpr (POST) {
           // post_v[j]^H x over the unit's stored points (the other vectors read 4 points at a
@@ -462,7 +582,7 @@ k_tp_rows(const cd* in, cd* out, TPArgs a, int nunits) {
         }
       }
     }
-    lds_barrier();  // the next unit's first exchange overwrites LDS
+    if constexpr (!PF) lds_barrier();  // the next unit's first exchange overwrites LDS
   }
   if constexpr (POST) {
     // one partial per workgroup and value: the waves' sums in a fixed order
@@ -662,8 +782,6 @@ __device__ __forceinline__ void dif_pairs(cd* v, cd w) {
 // fly during stage B', the twiddle and the stores; the next unit then loads only slots 8..15
 // from HBM and reads 0..7 back from LDS.  Barriers stay LDS-only (no vmcnt), so the DMA is not
 // drained early.
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
 // NX: x extent (row length in points) of the grid P2 runs on: TN for the complex apply, TN / 2
 // for the real-data plan's half spectrum (cfp_real.hip); y and z are TN long.
 // BL: the blocked intermediate layout of k_tp_rows<.., BLK = XT>: a unit's T columns c = x + XT y2
@@ -1786,6 +1904,13 @@ constexpr bool kRowsWave = true;
 // XCDs).  Whole apply (r05k, against a -DCFP_ROWS_XCD=0 build, alternating processes): 256^3
 // 3,361-3,388 against 3,288-3,316 PCApply/s, 512^3 282.3-282.5 against 274.6-275.4.
 constexpr bool kRowsXCD = CFP_ROWS_XCD != 0;
+// The one-GPU 256^3 row sweeps with the LDS-DMA prefetch of kRowsNPF of the next unit's 16 slots
+// (k_tp_rows<.., NPF>); -DCFP_ROWS_PF=0 builds the sweeps without it for A/B.
+#ifndef CFP_ROWS_PF
+#define CFP_ROWS_PF 8
+#endif
+constexpr int kRowsNPF = CFP_ROWS_PF;
+static_assert(kRowsNPF == 0 || (kRowsNPF >= 4 && kRowsNPF <= 8), "CFP_ROWS_PF: 0 (off) or 4 to 8 slots");
 
 // P1F / P3F: P1's load and P3's store policy out of place (kP1Flags / kP3Flags; 0 = plain)
 // WR: phase C's exchanges wave-local (F_WAVE_LDS)
@@ -1976,6 +2101,31 @@ bool three_pass_shape_valid(int n1, int mid, i64 n) {
          !(mid >= TP_MID_BLOCKED && n1 == 64);
 }
 
+// The 256^3 default row sweeps with the next unit's prefetch (k_tp_rows<.., kRowsNPF>): 0 where
+// they must not run -- the build without them, another layout than one GPU's natural one, a grid
+// that does not walk whole rounds (every workgroup then has the same number of units and only
+// its last one goes without a prefetch), or a source that is not 16-byte aligned (`in`: the
+// pointer the DMA reads in both sweeps) -- else the grid; the caller runs the plain sweeps on 0.
+static unsigned rows_pf_grid(const cd* in, const TPArgs& a) {
+  if (kRowsNPF == 0 || !kRowsXCD || !kRowsWave || !kRowsLP || a.lnyl != 0) return 0;
+  if (((uintptr_t)in & 15) != 0) return 0;
+  return grid_xcd(256 * 8, 2);
+}
+static void launch_rows_pf(int stage, const cd* in, cd* out, const TPArgs& a, hipStream_t s, unsigned g) {
+  if constexpr (kRowsNPF > 0) {
+    constexpr int W = F_WAVE_LDS, units = 256 * 8;
+    if (stage == 0 && in == out)
+      TP_LAUNCH((k_tp_rows<false, kP1InPlaceFlags | W, 32, 256, 16, true, true, 0, true, 0, 0, kRowsNPF>), dim3(g),
+                dim3(512), s, in, out, a, units);
+    else if (stage == 0)
+      TP_LAUNCH((k_tp_rows<false, kP1Flags | W, 32, 256, 16, true, true, 0, true, 0, 0, kRowsNPF>), dim3(g), dim3(512), s,
+                in, out, a, units);
+    else
+      TP_LAUNCH((k_tp_rows<true, kP3Flags | W, 32, 256, 16, true, true, 0, true, 0, 0, kRowsNPF>), dim3(g), dim3(512), s,
+                in, out, a, units);
+  }
+}
+
 hipError_t launch_three_pass(int stage, int n, const cd* in, cd* out, const TPArgs& a, TPShape shape,
                              hipStream_t s) {
   // TP_MID_ROWSALT: the default shape with the other phase-C exchanges in P1 / P3 (A/B)
@@ -2119,6 +2269,8 @@ hipError_t launch_three_pass(int stage, int n, const cd* in, cd* out, const TPAr
     }
   } else if (n1 == 64) {
     launch_rows<64, 256, 1>(stage, in, out, a, s);
+  } else if (const unsigned gpf = ra ? 0 : rows_pf_grid(in, a)) {
+    launch_rows_pf(stage, in, out, a, s, gpf);
   } else {
     launch_rows_ab<32, 256, 2, 16, true, kRowsLP>(ra, stage, in, out, a, s);
   }
