@@ -56,6 +56,9 @@ def _declare(L) -> None:
         "cfp_rplan_create": ([P(vp), i64, i64, i64, c_int], c_int),
         "cfp_rplan_destroy": ([vp], c_int),
         "cfp_rplan_set_symbol_transport": ([vp, P(ctypes.c_double)], c_int),
+        "cfp_rplan_set_symbol_advdiff": ([vp, P(ctypes.c_double), P(ctypes.c_double)], c_int),
+        "cfp_rplan_set_mid_kernel": ([vp, c_int], c_int),
+        "cfp_rplan_mid_kernel": ([vp, P(c_int)], c_int),
         "cfp_rplan_apply": ([vp, vp, vp, vp], c_int),
         "cfp_rplan_num_passes": ([vp, P(c_int)], c_int),
         "cfp_rplan_time_passes": ([vp, vp, vp, c_int, P(ctypes.c_double), vp], c_int),

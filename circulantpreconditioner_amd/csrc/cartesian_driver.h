@@ -10,13 +10,13 @@
 #include <sys/time.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../include/circulant_fft.h"
 #include "../../include/petsc_mini.h"
-#include "../../include/transport_equation.h"
 
 namespace cfp_driver {
 
@@ -33,6 +33,43 @@ void grid_spacing(const Config* cfg, double h[3]) {
   h[2] = (cfg->xmax[2] - cfg->xmin[2]) / (double)cfg->nz;
 }
 
+// The CSR builders write (re, im) pairs of doubles.  A complex PetscScalar is one pair; a real
+// one (-DCFP_REAL_SCALAR) takes kPairScalars = 2 scalars of room per value, and pairs_to_scalars
+// then keeps the real parts, in place (the operators are real: every imaginary part is 0).
+constexpr size_t kPairScalars = 2 * sizeof(double) / sizeof(PetscScalar);
+inline void pairs_to_scalars(PetscScalar* val, int64_t n) {
+  if constexpr (kPairScalars == 2)
+    for (int64_t k = 0; k < n; ++k) val[k] = val[2 * k];
+}
+
+// U = the shock initial condition on this rank's cells (initial_conditions_shock_cartesian,
+// include/transport_equation.h, is this function)
+inline PetscErrorCode shock_initial_conditions(PetscInt nx, PetscInt ny, PetscInt nz, const PetscReal xmin[3],
+                                               const PetscReal xmax[3], Vec U) {
+  PetscCheck(xmin && xmax, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "NULL domain bounds");
+  PetscInt n, Ng, lo;
+  PetscCall(VecGetLocalSize(U, &n));
+  PetscCall(VecGetSize(U, &Ng));
+  PetscCall(VecGetOwnershipRange(U, &lo, NULL));
+  PetscCheck(Ng == nx * ny * nz, PETSC_COMM_SELF, PETSC_ERR_ARG_SIZ, "U size differs from nx*ny*nz");
+  const double hx = (xmax[0] - xmin[0]) / (double)nx, hy = (xmax[1] - xmin[1]) / (double)ny,
+               hz = (xmax[2] - xmin[2]) / (double)nz;
+  const double cx = (xmin[0] + xmax[0]) / 2, cy = (xmin[1] + xmax[1]) / 2, cz = (xmin[2] + xmax[2]) / 2;
+  const double rmax = 0.3;
+  PetscScalar* u;
+  PetscCall(VecGetArrayWrite(U, &u));
+  for (PetscInt c = lo; c < lo + n; ++c) {  // this rank's cells
+    const PetscInt i = c % nx, j = (c / nx) % ny, k = c / (nx * ny);
+    const double x = xmin[0] + (i + 0.5) * hx, y = xmin[1] + (j + 0.5) * hy, z = xmin[2] + (k + 0.5) * hz;
+    double r2 = (x - cx) * (x - cx);
+    if (ny > 1) r2 += (y - cy) * (y - cy);
+    if (nz > 1) r2 += (z - cz) * (z - cz);
+    u[c - lo] = std::sqrt(r2) < rmax ? 650.0 : 600.0;
+  }
+  PetscCall(VecRestoreArrayWrite(U, &u));
+  return PETSC_SUCCESS;
+}
+
 // Un and dUn with the shock initial condition in Un.  One rank (P = 1): sequential Vecs;
 // several: the reference's VecCreateMPI on PETSC_COMM_WORLD with PETSC_DECIDE rows (:59-84)
 template <class Config>
@@ -43,16 +80,16 @@ PetscErrorCode create_state(const Config* cfg, int P, Vec* Un, Vec* dUn) {
   else if (cfg->on_device) PetscCall(VecCreateSeqHIP(PETSC_COMM_SELF, N, Un));
   else PetscCall(VecCreateSeq(PETSC_COMM_SELF, N, Un));
   PetscCall(VecDuplicate(*Un, dUn));
-  PetscCall(initial_conditions_shock_cartesian(cfg->nx, cfg->ny, cfg->nz, cfg->xmin, cfg->xmax, *Un));
+  PetscCall(shock_initial_conditions(cfg->nx, cfg->ny, cfg->nz, cfg->xmin, cfg->xmax, *Un));
   return PETSC_SUCCESS;
 }
 
-// this rank's n rows of Un (all of them on one rank) -> U_out, if the caller asked for them
+// this rank's n rows of Un (all of them on one rank) -> U_out (n PetscScalars), if the caller asked for them
 inline PetscErrorCode copy_out(Vec Un, PetscInt n, double* U_out) {
   if (!U_out) return PETSC_SUCCESS;
   const PetscScalar* u;
   PetscCall(VecGetArrayRead(Un, &u));
-  std::memcpy(U_out, (const void*)u, sizeof(double) * 2 * (size_t)n);
+  std::memcpy(U_out, (const void*)u, sizeof(PetscScalar) * (size_t)n);
   PetscCall(VecRestoreArrayRead(Un, &u));
   return PETSC_SUCCESS;
 }
@@ -66,9 +103,10 @@ PetscErrorCode aij_from_rows(MPI_Comm comm, int64_t N, RowsFn rows_fn, Mat* A) {
   PetscCall(MatGetOwnershipRange(*A, &lo, &hi));
   const int64_t m = hi - lo;
   std::vector<int64_t> rowptr((size_t)m + 1), col((size_t)(7 * (m > 0 ? m : 1)));
-  std::vector<PetscScalar> val((size_t)(7 * (m > 0 ? m : 1)));
+  std::vector<PetscScalar> val((size_t)(7 * (m > 0 ? m : 1)) * kPairScalars);
   int64_t nnz = 0;
   PetscCall(rows_fn((int64_t)lo, (int64_t)hi, rowptr.data(), col.data(), reinterpret_cast<double*>(val.data()), &nnz));
+  pairs_to_scalars(val.data(), nnz);
   for (int64_t r = 0; r < m; ++r) {
     const PetscInt row = lo + r, k = rowptr[(size_t)r + 1] - rowptr[(size_t)r];
     PetscCall(MatSetValues(*A, 1, &row, k, col.data() + rowptr[(size_t)r], val.data() + rowptr[(size_t)r], ADD_VALUES));

@@ -156,16 +156,18 @@ void advdiff_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, std::
     }
 }
 // k_tp_mid_rec2's column table at 256^3 (cfp_three_pass.h): [unit u][a, r = 256 / beta, b][lane],
-// lane = x + 8 y2 holding column kx = 8 (u % 32) + x, ky = u / 32 + 32 brev3(y2)
+// lane = x + 8 y2 holding column kx = 8 (u % nxt) + x, ky = u / nxt + 32 brev3(y2); nxt x tiles
+// per row: 32 on the complex grid (1024 units), 16 on the real plan's half spectrum (512 units)
 std::vector<cd> advdiff_z_table(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz,
-                                std::complex<double> mz) {
+                                std::complex<double> mz, int nxt) {
   const std::complex<double> p = lz + mz, q = mz;
-  std::vector<cd> t((size_t)kRec2TabLen);
-  for (int u = 0; u < 1024; ++u)
+  const int units = 32 * nxt;
+  std::vector<cd> t((size_t)units * 3 * 64);
+  for (int u = 0; u < units; ++u)
     for (int lane = 0; lane < 64; ++lane) {
       const int x = lane & 7, y2 = lane >> 3;
       const int k2 = ((y2 & 1) << 2) | (y2 & 2) | (y2 >> 2);
-      const std::complex<double> be = advdiff_z_beta(sx[(size_t)(8 * (u % 32) + x)], sy[(size_t)(u / 32 + 32 * k2)], p, q);
+      const std::complex<double> be = advdiff_z_beta(sx[(size_t)(8 * (u % nxt) + x)], sy[(size_t)(u / nxt + 32 * k2)], p, q);
       const std::complex<double> a = p / be, b = q / be, r = 256.0 / be;
       t[(size_t)((3 * u) * 64 + lane)] = make_cd(a.real(), a.imag());
       t[(size_t)((3 * u + 1) * 64 + lane)] = make_cd(r.real(), r.imag());
@@ -173,8 +175,7 @@ std::vector<cd> advdiff_z_table(const std::vector<cd>& sx, const std::vector<cd>
     }
   return t;
 }
-// two scans, eps / ((1 - |a|) (1 - |b|)): this cap keeps 8 eps / (1 - r)^2 at 2.9e-11
-constexpr double kZrec2MaxRatio = 1.0 - 1.0 / 128.0;
+// (the cap of both ratios: kZrec2MaxRatio, cfp_host.h)
 
 int ilog2_exact(i64 v) {
   if (v <= 0 || (v & (v - 1))) return -1;
@@ -873,7 +874,7 @@ extern "C" int cfp_plan_set_symbol_advdiff(cfp_plan_t p, const double lam[6], co
       double r[2];
       advdiff_z_ratio(p->sym1d[0], p->sym1d[1], lz, mz, r);
       if (r[0] <= kZrec2MaxRatio && r[1] <= kZrec2MaxRatio) {
-        const std::vector<cd> t = advdiff_z_table(p->sym1d[0], p->sym1d[1], lz, mz);
+        const std::vector<cd> t = advdiff_z_table(p->sym1d[0], p->sym1d[1], lz, mz, 32);
         if (!p->zrec2_tab) HIPCHK(hipMalloc(&p->zrec2_tab, sizeof(cd) * t.size()));
         HIPCHK(hipMemcpy(p->zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
         p->zrec2_ok = true;

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <complex>
 #include <memory>
 #include <vector>
 
@@ -157,12 +158,28 @@ struct cfp_rplan_s {
   cd* colsym3 = nullptr;  // [kx + M ky], kx < M
   cd* axsym3 = nullptr;   // [kz]
   cd* colsymq = nullptr;  // [ky] of the Nyquist column kx = M
+  // the advection-diffusion symbol at 256^3 (cfp_rplan_set_symbol_advdiff with mu_z != 0 and both
+  // z ratios under the cap): the half spectrum's column table of k_tp_mid_rec2_half
+  // (cfp_three_pass.h launch_three_pass_real_rec2; allocated with the first eligible symbol)
+  cd* zrec2_tab = nullptr;
+  bool zrec2_ok = false;
+  int mid = CFP_RMID_AUTO;  // cfp_rplan_set_mid_kernel
 };
 
 static bool three_ok(const cfp_rplan_s* p) {
   return p->n[0] == p->n[1] && p->n[1] == p->n[2] && (p->n[0] == 128 || p->n[0] == 256);
 }
 static bool use_three(const cfp_rplan_s* p) { return three_ok(p) && p->schedule != CFP_RSCHEDULE_FIVE; }
+// CFP_RMID_AUTO: the recurrence wherever it is eligible.  Measured on one MI355X against the FFT
+// kernel in the same process on three symbols (DESIGN.md "256^3 real P2",
+// profiles/r12_real_zrec2_ab.txt): the half-spectrum stage 69-72 -> 52-53 us, 6,237-6,304 against
+// 5,623-5,693 real PCApply/s (+10.0 to +10.9 %; spread inside a variant <= 0.2 %).
+constexpr bool kRealRec2Auto = true;
+// the next apply's half-spectrum stage is the two-sided z recurrence
+static bool use_zrec2(const cfp_rplan_s* p) {
+  return use_three(p) && p->n[0] == 256 && p->zrec2_ok && p->mid != CFP_RMID_FFT &&
+         (p->mid == CFP_RMID_REC || kRealRec2Auto);
+}
 
 namespace {
 struct RGuard {
@@ -187,10 +204,22 @@ void free_rplan(cfp_rplan_s* p) {
   if (p->colsym3) hipFree(p->colsym3);
   if (p->colsymq) hipFree(p->colsymq);
   if (p->axsym3) hipFree(p->axsym3);
+  if (p->zrec2_tab) hipFree(p->zrec2_tab);
   if (p->fork) hipEventDestroy(p->fork);
   if (p->join) hipEventDestroy(p->join);
   if (p->side) hipStreamDestroy(p->side);
   delete p;
+}
+
+// the 3-sweep schedule's tables (allocated with the first symbol)
+int upload_three(cfp_rplan_s* p, const std::vector<cd>& col, const std::vector<cd>& colq, const std::vector<cd>& ax) {
+  if (!p->colsym3) HIPCHK(hipMalloc(&p->colsym3, sizeof(cd) * col.size()));
+  if (!p->axsym3) HIPCHK(hipMalloc(&p->axsym3, sizeof(cd) * ax.size()));
+  if (!p->colsymq) HIPCHK(hipMalloc(&p->colsymq, sizeof(cd) * colq.size()));
+  HIPCHK(hipMemcpy(p->colsym3, col.data(), sizeof(cd) * col.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(p->axsym3, ax.data(), sizeof(cd) * ax.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(p->colsymq, colq.data(), sizeof(cd) * colq.size(), hipMemcpyHostToDevice));
+  return CFP_SUCCESS;
 }
 
 // 3 sweeps at 128^3 and 256^3: P1r (r2c rows + y1, also of the Nyquist column into Q) | P2 on the
@@ -207,7 +236,8 @@ int run_real_three(cfp_rplan_s* p, const double* b, double* x, hipStream_t s, st
   hipError_t e = launch_three_pass_real(0, (int)p->n[0], b, p->H, p->Q, nullptr, a, s, alt);
   if (e != hipSuccess) return hip_error(e, "r2c rows + y1 pass");
   if (ev) HIPCHK(hipEventRecord((*ev)[1], s));
-  e = launch_three_pass_real(1, (int)p->n[0], nullptr, p->H, nullptr, nullptr, a, s);
+  e = use_zrec2(p) ? launch_three_pass_real_rec2(p->H, a, p->zrec2_tab, s)
+                   : launch_three_pass_real(1, (int)p->n[0], nullptr, p->H, nullptr, nullptr, a, s);
   if (e != hipSuccess) return hip_error(e, "half-spectrum y2/z pass");
   if (ev) HIPCHK(hipEventRecord((*ev)[2], s));
   TPArgs aq = a;
@@ -222,7 +252,7 @@ int run_real_three(cfp_rplan_s* p, const double* b, double* x, hipStream_t s, st
 }
 
 int run_real(cfp_rplan_s* p, const double* b, double* x, hipStream_t s, std::vector<hipEvent_t>* ev) {
-  if (!p->has_sym) return set_error(CFP_ERR_ARG_WRONGSTATE, "no symbol set (call cfp_rplan_set_symbol_transport)");
+  if (!p->has_sym) return set_error(CFP_ERR_ARG_WRONGSTATE, "no symbol set (call cfp_rplan_set_symbol_transport or cfp_rplan_set_symbol_advdiff)");
   if (use_three(p)) return run_real_three(p, b, x, s, ev);
   const i64 rows = p->n[1] * p->n[2];
   const double sc = 2.0 / (double)(p->n[0] * p->n[1] * p->n[2]);
@@ -323,14 +353,65 @@ extern "C" int cfp_rplan_set_symbol_transport(cfp_rplan_t p, const double lam[3]
     for (i64 ky = 0; ky < ny; ++ky)
       colq[(size_t)ky] = make_cd(lam[0] * hx[(size_t)M].x + lam[1] * hy[(size_t)ky].x,
                                  lam[0] * hx[(size_t)M].y + lam[1] * hy[(size_t)ky].y);
-    if (!p->colsym3) HIPCHK(hipMalloc(&p->colsym3, sizeof(cd) * col.size()));
-    if (!p->axsym3) HIPCHK(hipMalloc(&p->axsym3, sizeof(cd) * ax.size()));
-    if (!p->colsymq) HIPCHK(hipMalloc(&p->colsymq, sizeof(cd) * colq.size()));
-    HIPCHK(hipMemcpy(p->colsym3, col.data(), sizeof(cd) * col.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->axsym3, ax.data(), sizeof(cd) * ax.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->colsymq, colq.data(), sizeof(cd) * colq.size(), hipMemcpyHostToDevice));
+    CFPCHK(upload_three(p, col, colq, ax));
+  }
+  p->zrec2_ok = false;
+  p->has_sym = true;
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_rplan_set_symbol_advdiff(cfp_rplan_t p, const double lam[3], const double mu[3]) {
+  if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  // the axes' parts in closed form, lambda and mu folded in (unit weights below)
+  std::vector<cd> s[3];
+  for (int a = 0; a < 3; ++a) s[a] = host_advdiff_symbol(p->n[a], {lam[a], 0.0}, {mu[a], 0.0});
+  const double one6[6] = {1.0, 0.0, 1.0, 0.0, 1.0, 0.0};
+  // half spectrum kx < nx/2, and the Nyquist column kx = nx/2
+  CFPCHK(cfp_plan_set_symbol_separable(p->main, (const double*)s[0].data(), (const double*)s[1].data(),
+                                       (const double*)s[2].data(), one6));
+  CFPCHK(cfp_plan_set_symbol_separable(p->nyq, (const double*)&s[0][(size_t)p->M], (const double*)s[1].data(),
+                                       (const double*)s[2].data(), one6));
+  p->zrec2_ok = false;
+  if (three_ok(p)) {  // the 3-sweep tables: colsym [kx + M ky] = s_x[kx] + s_y[ky], axsym = s_z
+    RGuard g(p->device);
+    const i64 M = p->M, ny = p->n[1];
+    std::vector<cd> col((size_t)(M * ny)), colq((size_t)ny);
+    for (i64 ky = 0; ky < ny; ++ky) {
+      for (i64 kx = 0; kx < M; ++kx)
+        col[(size_t)(kx + M * ky)] =
+            make_cd(s[0][(size_t)kx].x + s[1][(size_t)ky].x, s[0][(size_t)kx].y + s[1][(size_t)ky].y);
+      colq[(size_t)ky] = make_cd(s[0][(size_t)M].x + s[1][(size_t)ky].x, s[0][(size_t)M].y + s[1][(size_t)ky].y);
+    }
+    CFPCHK(upload_three(p, col, colq, s[2]));
+    if (p->n[0] == 256 && mu[2] != 0.0) {  // the one grid k_tp_mid_rec2_half is built for
+      // real lambda, mu: a half-spectrum column and its mirror have conjugate factors, so the
+      // full grid's ratios are the half's
+      double r[2];
+      advdiff_z_ratio(s[0], s[1], {lam[2], 0.0}, {mu[2], 0.0}, r);
+      if (r[0] <= kZrec2MaxRatio && r[1] <= kZrec2MaxRatio) {
+        const std::vector<cd> t = advdiff_z_table(s[0], s[1], {lam[2], 0.0}, {mu[2], 0.0}, (int)(M / 8));
+        if (t.size() != (size_t)kRealRec2TabLen) return set_error(CFP_ERR_LIB, "recurrence table size");
+        if (!p->zrec2_tab) HIPCHK(hipMalloc(&p->zrec2_tab, sizeof(cd) * t.size()));
+        HIPCHK(hipMemcpy(p->zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
+        p->zrec2_ok = true;
+      }
+    }
   }
   p->has_sym = true;
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_rplan_set_mid_kernel(cfp_rplan_t p, int mid) {
+  if (!p) return set_error(CFP_ERR_ARG_NULL, "NULL plan");
+  if (mid != CFP_RMID_AUTO && mid != CFP_RMID_FFT && mid != CFP_RMID_REC)
+    return set_error(CFP_ERR_ARG_OUTOFRANGE, "unknown real-plan middle kernel %d", mid);
+  p->mid = mid;
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_rplan_mid_kernel(cfp_rplan_t p, int* kind) {
+  if (!p || !kind) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  *kind = use_zrec2(p) ? CFP_MID_KERNEL_ZREC2 : CFP_MID_KERNEL_FFT;
   return CFP_SUCCESS;
 }
 

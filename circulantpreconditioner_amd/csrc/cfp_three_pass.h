@@ -110,6 +110,12 @@ hipError_t launch_three_pass_slab(int stage, int n, const cd* in, cd* out, const
 // inverse (slot layout, as H).
 hipError_t launch_three_pass_real(int stage, int n, const double* b, cd* H, cd* Q, double* x, const TPArgs& a,
                                   hipStream_t s, bool alt_rows = false);
+// stage 1 of the 256^3 real plan for the advection-diffusion symbol: the two-sided z recurrence
+// on H (k_tp_mid_rec2's unit on rows of 128 points).  tab2 (device, 16-byte aligned) as for
+// launch_three_pass_rec2 with 512 units: unit u holds kx = 8 (u % 16) + x, ky = u / 16 +
+// 32 brev3(y2).  H must be 16-byte aligned; the caller has checked both z ratios.
+constexpr int kRealRec2TabLen = 512 * 3 * 64;
+hipError_t launch_three_pass_real_rec2(cd* H, const TPArgs& a, const cd* tab2, hipStream_t s);
 
 // wave-system plan (cfp_wave_three.hip): the 3-sweep apply of the interleaved 4-component field
 // (idx = 4 cell + comp) on a 128^3 grid, y split 16 x 8.  stage 0 P1w (in -> out), 1 P2w (out in

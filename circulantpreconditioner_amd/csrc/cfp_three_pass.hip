@@ -1135,14 +1135,16 @@ __device__ __forceinline__ void y2_inv_pair(cd& vp, cd& vq, cd w, cd w8, cd w4, 
 // row 8 k1; slot m: z = 16 wv + m) + this lane's 32-bit byte offset loff (x, row y2): a scalar
 // base plus one offset register for all 16 slots, instead of 16 address pairs.  The callers pass
 // opaque copies of u and loff, so that the addresses are formed again at each phase.
-struct Tile {
-  static constexpr int TN = 256, N2 = 8, XT = 8, NXT = TN / XT;
+// NX: the row length in points (256; the real plan's half spectrum: 128, with loff on rows of NX).
+template <int NX>
+struct TileT {
+  static constexpr int TN = 256, N2 = 8, XT = 8, NXT = NX / XT;
   cd* data;
   i64 zs;
   int wv;
   double* pf_l;
   __device__ __forceinline__ cd* slot_ptr(int u, int m) const {
-    return data + ((u % NXT) * XT + (i64)TN * N2 * (u / NXT) + zs * (16 * wv + m));
+    return data + ((u % NXT) * XT + (i64)NX * N2 * (u / NXT) + zs * (16 * wv + m));
   }
   // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
   template <int NPF, int LD>
@@ -1164,6 +1166,7 @@ struct Tile {
   }
   __device__ __forceinline__ void store(int u, int m, unsigned loff, cd v) const { gstore<0>(at(slot_ptr(u, m), loff), v); }
 };
+using Tile = TileT<256>;
 }  // namespace rec
 
 template <int PROBE, bool PF, int LD>
@@ -1374,18 +1377,27 @@ k_tp_mid_rec(cd* data, TPArgs a, int nunits) {
 // waits into vmcnt(0)); the next unit's first barrier publishes it.  Three buffers: the one
 // written at a unit's end was last read two units earlier.  The host enables the kernel where
 // max(|a|, |b|) <= 1 - 2^-7 on every column.
-template <int PROBE, bool PF, int LD>
+//
+// NX = 128 (k_tp_mid_rec2_half): the same unit on the real plan's half spectrum H (128 x, 256 y,
+// 256 z: rows of NX points, 16 x tiles per row, 512 units, tab2 with 512 units); XCD: units in
+// xcd_unit order (the host launches whole rounds), as the FFT kernel of that stage runs.
+template <int PROBE, bool PF, int LD, int NX = 256, bool XCD = false>
 __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TPArgs& a, int nunits,
                                                  double* __restrict__ pf_l, cd* __restrict__ carr,
                                                  cd* __restrict__ ctab, cd* __restrict__ tw_l,
                                                  const cd* __restrict__ tab2) {
-  constexpr int TN = 256, NXT = rec::Tile::NXT, NW = 16;
+  constexpr int TN = 256, NXT = rec::TileT<NX>::NXT, NW = 16;
   constexpr int NPF = PF ? kRecNPF : 0;
   const int tid = threadIdx.x;
   const int lane = tid & 63, x = lane & 7, y2 = lane >> 3;
   const int wv = __builtin_amdgcn_readfirstlane(tid / 64);
-  const i64 zs = (i64)TN << (a.lnyl ? a.lnyl : ilog2(TN));
+  const i64 zs = (i64)NX << (a.lnyl ? a.lnyl : ilog2(TN));
   using rec::at, rec::pin, rec::cfma;
+  // the unit of persistent-grid iteration `it`
+  const auto unit_of = [](int it) {
+    if constexpr (XCD) return xcd_unit(it, (int)gridDim.x);
+    else return it;
+  };
   // unit u's a, r, b of the host's table -> ctab[buf] by LDS-DMA, lane-linear (wave 0)
   const auto tab_fetch = [&](int u, int buf) {
     unsigned lo = 16u * (unsigned)lane;
@@ -1397,15 +1409,15 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
   };
   if (tid < TN) tw_l[tid] = a.tw[tid];
   if (wv == 0 && (int)blockIdx.x < nunits) {  // the first two units' tables
-    tab_fetch((int)blockIdx.x, 0);
-    if ((int)(blockIdx.x + gridDim.x) < nunits) tab_fetch((int)(blockIdx.x + gridDim.x), 1);
+    tab_fetch(unit_of((int)blockIdx.x), 0);
+    if ((int)(blockIdx.x + gridDim.x) < nunits) tab_fetch(unit_of((int)(blockIdx.x + gridDim.x)), 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
-  const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);  // this lane's (x, row y2)
-  const rec::Tile tile{data, zs, wv, pf_l};
+  const unsigned loff = 16u * ((unsigned)x + (unsigned)NX * (unsigned)y2);  // this lane's (x, row y2)
+  const rec::TileT<NX> tile{data, zs, wv, pf_l};
   if constexpr (PF) {
-    if ((int)blockIdx.x < nunits) tile.prefetch<NPF, LD>((int)blockIdx.x, loff);
+    if ((int)blockIdx.x < nunits) tile.template prefetch<NPF, LD>(unit_of((int)blockIdx.x), loff);
   }
   // the y2 DFT's per-lane constants (rec::y2_fwd_pair)
   const double s3 = (y2 & 1) ? -1.0 : 1.0;
@@ -1426,7 +1438,7 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
   int buf = 0;
   const auto unit = [&](const int it, auto more_c) {
     constexpr bool more = decltype(more_c)::value;
-    const int u = it;
+    const int u = unit_of(it);
     const int k1 = a.k1_off + u / NXT;  // global k1
     const int nbuf = buf == 2 ? 0 : buf + 1;
     cd v[16];
@@ -1437,14 +1449,14 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
       if constexpr (PF) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA landed
 #pragma unroll
-        for (int m = 0; m < NPF; ++m) v[m] = tile.prefetched<NPF>(m, idx(lane));
+        for (int m = 0; m < NPF; ++m) v[m] = tile.template prefetched<NPF>(m, idx(lane));
       }
       {
         int ul = u;
         unsigned lo1 = loff;
         asm volatile("" : "+s"(ul), "+v"(lo1));  // scalar base + this register, formed here
 #pragma unroll
-        for (int m = NPF; m < 16; ++m) v[m] = tile.load<LD>(ul, m, lo1);
+        for (int m = NPF; m < 16; ++m) v[m] = tile.template load<LD>(ul, m, lo1);
       }
     }
     // twiddle W_256^{y2 k1}
@@ -1529,8 +1541,9 @@ __device__ __forceinline__ void tp_mid_rec2_body(cd* __restrict__ data, const TP
       // and the table of the unit after it (nobody reads that buffer any more: its last readers
       // passed this unit's second barrier)
       if constexpr (more) {
-        if constexpr (PF && !(PROBE & PR_NO_LOAD)) tile.prefetch<NPF, LD>(it + (int)gridDim.x, loff);
-        if (wv == 0 && it + 2 * (int)gridDim.x < nunits) tab_fetch(it + 2 * (int)gridDim.x, nbuf == 2 ? 0 : nbuf + 1);
+        if constexpr (PF && !(PROBE & PR_NO_LOAD)) tile.template prefetch<NPF, LD>(unit_of(it + (int)gridDim.x), loff);
+        if (wv == 0 && it + 2 * (int)gridDim.x < nunits)
+          tab_fetch(unit_of(it + 2 * (int)gridDim.x), nbuf == 2 ? 0 : nbuf + 1);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (!(PROBE & PR_NO_STORE)) {
@@ -1563,6 +1576,18 @@ k_tp_mid_rec2(cd* data, TPArgs a, int nunits, const cd* tab2) {
   __shared__ __attribute__((aligned(16))) cd ctab[3 * 3 * 64];   // the columns' a, r and b [unit mod 3][a, r, b][column]
   __shared__ cd tw_l[256];
   tp_mid_rec2_body<PROBE, PF, LD>(data, a, nunits, pf_l, carr, ctab, tw_l, tab2);
+}
+
+// the same on the real plan's half spectrum H (rows of 128 points, 512 units; cfp_three_pass.h
+// launch_three_pass_real_rec2).  H is plan-owned and 16-byte aligned: the prefetching body only.
+template <bool XCD, int LD = 0>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
+k_tp_mid_rec2_half(cd* data, TPArgs a, int nunits, const cd* tab2) {
+  __shared__ __attribute__((aligned(16))) double pf_l[16 * kRecNPF * 128];
+  __shared__ __attribute__((aligned(16))) cd carr[2 * 16 * 64];
+  __shared__ __attribute__((aligned(16))) cd ctab[3 * 3 * 64];
+  __shared__ cd tw_l[256];
+  tp_mid_rec2_body<0, true, LD, 128, XCD>(data, a, nunits, pf_l, carr, ctab, tw_l, tab2);
 }
 
 
@@ -2274,6 +2299,23 @@ hipError_t launch_three_pass(int stage, int n, const cd* in, cd* out, const TPAr
   } else {
     launch_rows_ab<32, 256, 2, 16, true, kRowsLP>(ra, stage, in, out, a, s);
   }
+  return hipGetLastError();
+}
+
+// (Last in the file: the kernel it instantiates is then emitted behind every other function, whose
+// assembly stays the parent's label for label, tools/isa_same.py.)
+// The half-spectrum stage 1 of the real plan at 256^3 by the two-sided recurrence.  Unit order:
+// linear or the XCD order of that stage's FFT kernel (CFP_REAL_MID_XCD), by measurement
+// (profiles/r12_real_zrec2_ab.txt); -DCFP_REAL_REC2_XCD=0/1 builds the other for A/B.
+#ifndef CFP_REAL_REC2_XCD
+#define CFP_REAL_REC2_XCD 1
+#endif
+hipError_t launch_three_pass_real_rec2(cd* H, const TPArgs& a, const cd* tab2, hipStream_t s) {
+  constexpr int units = (128 / 8) * 32;  // x tiles of the half spectrum x k1
+  static_assert(units * 3 * 64 == kRealRec2TabLen, "the table of launch_three_pass_real_rec2");
+  const unsigned gx = CFP_REAL_REC2_XCD ? grid_xcd(units, 1) : 0;
+  if (gx) TP_LAUNCH((k_tp_mid_rec2_half<true, kP2LoadFlags>), dim3(gx), dim3(1024), s, H, a, units, tab2);
+  else TP_LAUNCH((k_tp_mid_rec2_half<false, kP2LoadFlags>), dim3(grid_of(units, 1)), dim3(1024), s, H, a, units, tab2);
   return hipGetLastError();
 }
 

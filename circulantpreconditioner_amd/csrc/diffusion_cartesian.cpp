@@ -9,6 +9,11 @@
 // apply and the destroy callbacks are the transport ones: what they do (the solve with the plan's
 // own symbol while Diag is untouched, the objects setup made) does not depend on which closed form
 // filled the plan.  Only setup differs: it sets the advection-diffusion symbol.
+//
+// Compiled into both libraries (PetscScalar complex, and double with -DCFP_REAL_SCALAR).  What
+// depends on the build sits behind cfp_pc::pc_set_advdiff_symbol and cfp_pc::pc_advdiff_diag
+// (pcshell_common.h; pcshell_fft3d.cpp, pcshell_fft3d_real.cpp): which plans take the symbol and
+// the layout of Diag.
 #ifndef CFP_WITH_PETSC
 #include <algorithm>
 #include <cmath>
@@ -50,7 +55,7 @@ PetscErrorCode ensure_advdiff_symbol(ShellBase* s, const double lam[6], const do
   std::memcpy(ad + 6, mu, 6 * sizeof(double));
   if (s->has_ad && s->symbol_version() == s->ad_version && std::memcmp(s->ad, ad, sizeof(ad)) == 0)
     return PETSC_SUCCESS;
-  CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
+  PetscCall(pc_set_advdiff_symbol(s, lam, mu));
   std::memcpy(s->ad, ad, sizeof(ad));
   s->has_ad = true;
   s->ad_version = s->symbol_version();
@@ -186,13 +191,7 @@ extern "C" PetscErrorCode setupFFTPrec3DDiffusion(PC pc) {
   pack6(ctx->lambda_x, ctx->lambda_y, ctx->lambda_z, lam);
   pack6(ctx->mu_x, ctx->mu_y, ctx->mu_z, mu);
   PetscCall(ensure_advdiff_symbol(s, lam, mu));
-  DevOut d;
-  PetscCall(d.get(ctx->Diag, s->nl));
-  int rc = cfp_plan_get_diag(s->plan, d.ptr(), nullptr);
-  if (rc == CFP_SUCCESS) rc = cfp_stream_sync(nullptr);
-  PetscCall(d.put());
-  CFPCALL(rc);
-  PetscCall(s->remember_diag(ctx->Diag));
+  PetscCall(pc_advdiff_diag(s, ctx->Diag, lam, mu));
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 
@@ -236,11 +235,12 @@ extern "C" PetscErrorCode computeAdvectionDiffusionMatrixCartesianAIJ(MPI_Comm c
   PetscCallMPI(MPI_Comm_size(comm, &P));
   if (P == 1) {  // one rank: the arrays go in whole (MATSEQAIJ, as computeDivergenceMatrixCartesian)
     std::vector<int64_t> rowptr((size_t)N + 1), col((size_t)(7 * N));
-    std::vector<PetscScalar> val((size_t)(7 * N));
+    std::vector<PetscScalar> val((size_t)(7 * N) * cfp_driver::kPairScalars);
     int64_t nnz = 0;
     const int rc = cfp_advdiff_csr(nx, ny, nz, h, dt, a, nu, (int)bc, 0.0, rowptr.data(), col.data(),
                                    reinterpret_cast<double*>(val.data()), &nnz);
     PetscCheck(rc == CFP_SUCCESS, PETSC_COMM_SELF, rc, "computeAdvectionDiffusionMatrixCartesianAIJ: bad arguments");
+    cfp_driver::pairs_to_scalars(val.data(), nnz);
     PetscCall(MatCreateSeqAIJWithArrays(comm, N, N, rowptr.data(), col.data(), val.data(), A));
     PetscFunctionReturn(PETSC_SUCCESS);
   }

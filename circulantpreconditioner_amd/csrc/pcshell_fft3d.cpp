@@ -344,6 +344,23 @@ PetscErrorCode cfp_pc::own_symbol_apply(Mat FFT_MAT, Vec X, Vec b) {
   return PETSC_SUCCESS;
 }
 
+// the diffusion boundary's build-specific pieces (pcshell_common.h): one complex plan; Diag is the
+// plan's own closed-form symbol on the full grid
+PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6]) {
+  CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
+  return PETSC_SUCCESS;
+}
+PetscErrorCode cfp_pc::pc_advdiff_diag(ShellBase* s, Vec Diag, const double*, const double*) {
+  DevOut d;
+  PetscCall(d.get(Diag, s->nl));
+  int rc = cfp_plan_get_diag(s->plan, d.ptr(), nullptr);
+  if (rc == CFP_SUCCESS) rc = cfp_stream_sync(nullptr);
+  PetscCall(d.put());
+  CFPCALL(rc);
+  PetscCall(s->remember_diag(Diag));
+  return PETSC_SUCCESS;
+}
+
 // ------------------------------------------------------------------ PCSHELL callbacks
 // the solve of applyFFT3DPrecTransport (pcshell_boundary.cpp)
 PetscErrorCode cfp_pc::pc_solve(PC pc, FFTPrecTransportContext* ctx, Vec X, Vec src) {

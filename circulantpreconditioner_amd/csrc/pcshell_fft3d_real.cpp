@@ -17,7 +17,9 @@
 // passes, c2r; 3 sweeps at 128^3 and 256^3) where it supports the grid, else the complex plan on
 // b promoted to complex (one extra read and write of N complex values).  An explicit Diag (any
 // change to the Diag setup made) takes the complex plan with the Hermitian extension of the
-// half-spectrum Diag.
+// half-spectrum Diag.  The diffusion boundary (diffusion_cartesian.cpp, include/diffusion_equation.h)
+// sets the advection-diffusion symbol on both plans through pc_set_advdiff_symbol below and takes
+// the same paths.
 //
 // Several ranks (r05; the reference's real branch runs on PETSC_COMM_WORLD
 // like the complex one, src/FftLinearSolver_3D.c:6-78,176,186 and src/PCSHELLFft_3D.cxx:34-35):
@@ -151,6 +153,13 @@ PetscErrorCode ensure_transport_symbol(RShell* s, const double lam[3]) {
   return PETSC_SUCCESS;
 }
 
+// rplan holds the complex plan's current symbol: the shell set both, last, by either setter
+// (ensure_transport_symbol's lam / lam_version, the diffusion boundary's ad / ad_version)
+bool rplan_current(const RShell* s) {
+  const uint64_t v = s->symbol_version();
+  return v == s->lam_version || (s->has_ad && v == s->ad_version);
+}
+
 // X = C^{-1} b with the plan's own symbol (own) or the half-spectrum Diag given; b may be X
 PetscErrorCode rshell_apply(RShell* s, Vec X, Vec b, bool own, Vec Diag) {
   PetscCall(ensure_bufs(s, !own));
@@ -174,7 +183,7 @@ PetscErrorCode rshell_apply(RShell* s, Vec X, Vec b, bool own, Vec Diag) {
       if (!rc) rc = cfp_complex_real_part(s->zbuf, xout.ptr(), s->nl, 1.0 / (double)s->N, q.st);
     }
     if (!rc) rc = cfp_stream_sync(q.st);
-  } else if (own && s->rplan && s->symbol_version() == s->lam_version) {  // the real plan: 8-byte grid values end to end
+  } else if (own && s->rplan && rplan_current(s)) {  // the real plan: 8-byte grid values end to end
     rc = cfp_rplan_apply(s->rplan, bin.ptr(), xout.ptr(), q.st);
   } else {  // the complex plan on the promoted b, real part out (x is real for a Hermitian symbol)
     rc = cfp_real_to_complex(bin.ptr(), s->zbuf, s->N, q.st);
@@ -192,15 +201,11 @@ PetscErrorCode rshell_apply(RShell* s, Vec X, Vec b, bool own, Vec Diag) {
   return PETSC_SUCCESS;
 }
 
-// the half-spectrum symbol 1 + sum_d lam_d c_d(k_d) on the host (c_d: the 1-D DFTs of the
-// transport columns, from their closed form), planes kz in [z0, z0 + nzl)
-std::vector<double> half_symbol(const PetscInt d[3], const double lam[3], PetscInt z0, PetscInt nzl) {
+// the half-spectrum symbol 1 + sum_d lam_d c_d(k_d) on the host, planes kz in [z0, z0 + nzl);
+// c_d: the axes' 1-D symbols (n_d interleaved complex values each), lam_d their weights
+std::vector<double> half_symbol(const PetscInt d[3], const std::vector<double> c[3], const double lam[3], PetscInt z0,
+                                PetscInt nzl) {
   const PetscInt nx = d[0], ny = d[1], M = nx / 2 + 1;
-  std::vector<double> c[3];
-  for (int a = 0; a < 3; ++a) {
-    c[a].resize(2 * (size_t)d[a]);
-    cfp_transport_symbol_1d(d[a], c[a].data());
-  }
   std::vector<double> h(2 * (size_t)(M * ny * nzl));
   for (PetscInt kz = z0; kz < z0 + nzl; ++kz)
     for (PetscInt ky = 0; ky < ny; ++ky)
@@ -329,6 +334,44 @@ extern "C" PetscErrorCode FftTransportSolver(PetscInt nx, PetscInt ny, PetscInt 
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 
+// X = C^{-1} b with the plans' own symbol (the diffusion direct solver)
+PetscErrorCode cfp_pc::own_symbol_apply(Mat FFT_MAT, Vec X, Vec b) {
+  RShell* s;
+  PetscCall(shell_of(FFT_MAT, &s));
+  PetscCall(check_size(X, s->nl, "own_symbol_apply: X has the wrong size"));
+  PetscCall(check_size(b, s->nl, "own_symbol_apply: b has the wrong size"));
+  ++s->solves_own;
+  PetscCall(rshell_apply(s, X, b, true, nullptr));
+  return PETSC_SUCCESS;
+}
+
+// The diffusion boundary's build-specific pieces (pcshell_common.h).  The symbol goes on the
+// complex plan (grids the real plan lacks, the explicit-Diag path) and on the real plan; the
+// caller (ensure_advdiff_symbol) then records ad / ad_version, which rplan_current reads.
+PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* base, const double lam[6], const double mu[6]) {
+  RShell* s = static_cast<RShell*>(base);
+  CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
+  const double l3[3] = {lam[0], lam[2], lam[4]}, m3[3] = {mu[0], mu[2], mu[4]};
+  if (s->rplan) CFPCALL(cfp_rplan_set_symbol_advdiff(s->rplan, l3, m3));
+  return PETSC_SUCCESS;
+}
+// Diag: the half spectrum [nz][ny][nx/2 + 1] of the symbol, from the axes' closed forms
+PetscErrorCode cfp_pc::pc_advdiff_diag(ShellBase* s, Vec Diag, const double lam[6], const double mu[6]) {
+  std::vector<double> c[3];
+  for (int a = 0; a < 3; ++a) {
+    c[a].resize(2 * (size_t)s->dims[a]);
+    CFPCALL(cfp_advdiff_symbol_1d(s->dims[a], lam + 2 * a, mu + 2 * a, c[a].data()));
+  }
+  const double one[3] = {1.0, 1.0, 1.0};
+  const std::vector<double> h = half_symbol(s->dims, c, one, s->z0, s->nzl);
+  PetscScalar* d;
+  PetscCall(VecGetArrayWrite(Diag, &d));
+  std::memcpy(d, h.data(), sizeof(double) * h.size());
+  PetscCall(VecRestoreArrayWrite(Diag, &d));
+  PetscCall(s->remember_diag(Diag));
+  return PETSC_SUCCESS;
+}
+
 // the solve of applyFFT3DPrecTransport (pcshell_boundary.cpp); no dots ride in a real apply
 PetscErrorCode cfp_pc::pc_solve(PC, FFTPrecTransportContext* ctx, Vec X, Vec src) {
   return solve_3D(ctx->FFT_MAT, X, ctx->Diag, src, ctx->b_hat, ctx->n_x * ctx->n_y * ctx->n_z);
@@ -355,7 +398,12 @@ extern "C" PetscErrorCode setupFFTPrec3D(PC pc) {
   PetscCall(shell_of(ctx->FFT_MAT, &s));
   const double lam[3] = {ctx->lambda_x, ctx->lambda_y, ctx->lambda_z};
   PetscCall(ensure_transport_symbol(s, lam));
-  const std::vector<double> h = half_symbol(s->dims, lam, s->z0, s->nzl);
+  std::vector<double> c[3];  // the 1-D DFTs of the transport columns, from their closed form
+  for (int a = 0; a < 3; ++a) {
+    c[a].resize(2 * (size_t)s->dims[a]);
+    cfp_transport_symbol_1d(s->dims[a], c[a].data());
+  }
+  const std::vector<double> h = half_symbol(s->dims, c, lam, s->z0, s->nzl);
   PetscScalar* d;
   PetscCall(VecGetArrayWrite(ctx->Diag, &d));
   std::memcpy(d, h.data(), sizeof(double) * h.size());

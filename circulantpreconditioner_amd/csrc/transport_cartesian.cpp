@@ -143,27 +143,7 @@ extern "C" PetscErrorCode computeDivergenceMatrixCartesianAIJ(MPI_Comm comm, Pet
 extern "C" PetscErrorCode initial_conditions_shock_cartesian(PetscInt nx, PetscInt ny, PetscInt nz,
                                                              const PetscReal xmin[3], const PetscReal xmax[3], Vec U) {
   PetscFunctionBeginUser;
-  PetscCheck(xmin && xmax, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "NULL domain bounds");
-  PetscInt n, Ng, lo;
-  PetscCall(VecGetLocalSize(U, &n));
-  PetscCall(VecGetSize(U, &Ng));
-  PetscCall(VecGetOwnershipRange(U, &lo, NULL));
-  PetscCheck(Ng == nx * ny * nz, PETSC_COMM_SELF, PETSC_ERR_ARG_SIZ, "U size differs from nx*ny*nz");
-  const double hx = (xmax[0] - xmin[0]) / (double)nx, hy = (xmax[1] - xmin[1]) / (double)ny,
-               hz = (xmax[2] - xmin[2]) / (double)nz;
-  const double cx = (xmin[0] + xmax[0]) / 2, cy = (xmin[1] + xmax[1]) / 2, cz = (xmin[2] + xmax[2]) / 2;
-  const double rmax = 0.3;
-  PetscScalar* u;
-  PetscCall(VecGetArrayWrite(U, &u));
-  for (PetscInt c = lo; c < lo + n; ++c) {  // this rank's cells
-    const PetscInt i = c % nx, j = (c / nx) % ny, k = c / (nx * ny);
-    const double x = xmin[0] + (i + 0.5) * hx, y = xmin[1] + (j + 0.5) * hy, z = xmin[2] + (k + 0.5) * hz;
-    double r2 = (x - cx) * (x - cx);
-    if (ny > 1) r2 += (y - cy) * (y - cy);
-    if (nz > 1) r2 += (z - cz) * (z - cz);
-    u[c - lo] = std::sqrt(r2) < rmax ? 650.0 : 600.0;
-  }
-  PetscCall(VecRestoreArrayWrite(U, &u));
+  PetscCall(cfp_driver::shock_initial_conditions(nx, ny, nz, xmin, xmax, U));
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 

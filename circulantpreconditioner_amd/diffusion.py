@@ -2,6 +2,10 @@
 its symbol inside the stand-in KSPGMRES, and the direct solver (include/diffusion_equation.h,
 csrc/diffusion_cartesian.cpp).  The mirror of transport.py for the operator the reference's to-do
 list asks for next.
+
+Both libraries hold these functions.  The default is the complex-scalar one; ``real=True`` runs
+the real-scalar library (petsc_real.py: PetscScalar = double, fields of N doubles, the real-data
+plan behind the PCSHELL).
 """
 from __future__ import annotations
 
@@ -25,8 +29,13 @@ def _d3(v) -> ctypes.Array:
     return (ctypes.c_double * 3)(*[float(x) for x in v])
 
 
+def _real_lib():
+    from . import petsc_real
+    return petsc_real
+
+
 def advdiff_csr(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[float], nu: float,
-                bc: str | int = "wall", shift: float = 0.0):
+                bc: str | int = "wall", shift: float = 0.0, real: bool = False):
     """(rowptr, col, val) of shift*I + dt (a . grad - nu lap) on the grid (host only): upwind
     advection with the conservative sign plus the centred 7-point diffusion; bc 'wall' skips the
     border faces, 'periodic' gives the circulant the FFT preconditioner inverts."""
@@ -38,32 +47,41 @@ def advdiff_csr(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[
     val = np.empty(7 * n, dtype=np.complex128)
     nnz = ctypes.c_int64()
     P64 = ctypes.POINTER(ctypes.c_int64)
-    check(lib().cfp_advdiff_csr(nx, ny, nz, _d3(h), float(dt), _d3(a), float(nu), b, float(shift),
-                                rowptr.ctypes.data_as(P64), col.ctypes.data_as(P64),
-                                val.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(nnz)))
+    fn = _real_lib().lib().cfp_advdiff_csr if real else lib().cfp_advdiff_csr
+    rc = fn(nx, ny, nz, _d3(h), float(dt), _d3(a), float(nu), b, float(shift), rowptr.ctypes.data_as(P64),
+            col.ctypes.data_as(P64), val.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(nnz))
+    if rc and real:
+        raise ValueError(f"cfp_advdiff_csr: bad arguments (code {rc})")
+    check(rc)
     k = nnz.value
     return rowptr, col[:k].copy(), val[:k].copy()
 
 
 def operator(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[float], nu: float,
-             bc: str | int = "wall", comm: int = PETSC_COMM_SELF) -> Mat:
+             bc: str | int = "wall", comm: int = PETSC_COMM_SELF, real: bool = False):
     """computeAdvectionDiffusionMatrixCartesianAIJ: dt (a . grad - nu lap) as a stand-in AIJ Mat
-    (no MatShift)."""
+    (no MatShift).  real=True: the real-scalar library's Mat handle (petsc_real.mat_mult,
+    petsc_real.mat_destroy)."""
     nx, ny, nz = (int(v) for v in dims)
     b = _BC[bc] if isinstance(bc, str) else int(bc)
     hdl = ctypes.c_void_p()
+    if real:
+        R = _real_lib()
+        R.PetscCall(R.lib().computeAdvectionDiffusionMatrixCartesianAIJ(int(comm), nx, ny, nz, _d3(h), float(dt),
+                                                                        _d3(a), float(nu), b, ctypes.byref(hdl)))
+        return hdl
     PetscCall(lib().computeAdvectionDiffusionMatrixCartesianAIJ(int(comm), nx, ny, nz, _d3(h), float(dt), _d3(a),
                                                                 float(nu), b, ctypes.byref(hdl)))
     return Mat(hdl)
 
 
-def config(n: int | Sequence[int] = 32, **kw) -> AdvDiffConfig:
+def config(n: int | Sequence[int] = 32, real: bool = False, **kw) -> AdvDiffConfig:
     """cfp_advdiff_config_default ([-0.5, 0.5]^3, a = (1, 0, 0), nu = 0.01, dt = 0.01, one step,
     precision 1e-8, the FFT PCSHELL, walls) with keyword overrides: pc='none'|'fft',
     bc='wall'|'periodic', steps=ntmax, device=True/False, plus any AdvDiffConfig field."""
     cfg = AdvDiffConfig()
     dims = (int(n),) * 3 if np.isscalar(n) else tuple(int(v) for v in n)
-    lib().cfp_advdiff_config_default(ctypes.byref(cfg), dims[0])
+    (_real_lib().lib() if real else lib()).cfp_advdiff_config_default(ctypes.byref(cfg), dims[0])
     cfg.nx, cfg.ny, cfg.nz = dims
     for k, v in kw.items():
         if k == "pc":
@@ -84,26 +102,31 @@ def config(n: int | Sequence[int] = 32, **kw) -> AdvDiffConfig:
     return cfg
 
 
-def _run(fn, cfg: AdvDiffConfig, return_field: bool):
+def _run(name: str, cfg: AdvDiffConfig, return_field: bool, real: bool):
     res = AdvDiffResult()
     n = int(cfg.nx * cfg.ny * cfg.nz)
-    out = np.empty(n, dtype=np.complex128) if return_field else None
+    out = np.empty(n, dtype=np.float64 if real else np.complex128) if return_field else None
     ptr = out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if out is not None else None
-    PetscCall(fn(ctypes.byref(cfg), ctypes.byref(res), ptr))
+    if real:
+        R = _real_lib()
+        R.PetscCall(getattr(R.lib(), name)(ctypes.byref(cfg), ctypes.byref(res), ptr))
+    else:
+        PetscCall(getattr(lib(), name)(ctypes.byref(cfg), ctypes.byref(res), ptr))
     d = res.as_dict()
     return (d, out) if return_field else d
 
 
-def run(cfg: AdvDiffConfig, return_field: bool = False):
+def run(cfg: AdvDiffConfig, return_field: bool = False, real: bool = False):
     """AdvectionDiffusionGMRES: the implicit time loop with the stand-in GMRES and PCNONE or the
-    diffusion PCSHELL; returns the result dict (and the final field when asked)."""
-    return _run(lib().AdvectionDiffusionGMRES, cfg, return_field)
+    diffusion PCSHELL; returns the result dict (and the final field when asked: N complex values,
+    or N doubles with real=True, the real-scalar library)."""
+    return _run("AdvectionDiffusionGMRES", cfg, return_field, real)
 
 
-def run_direct(cfg: AdvDiffConfig, return_field: bool = False):
+def run_direct(cfg: AdvDiffConfig, return_field: bool = False, real: bool = False):
     """AdvectionDiffusionFFTDirect: one PetscFft3DDiffusionSolver(ctx, Un, Un) per implicit step
-    (the periodic operator)."""
-    return _run(lib().AdvectionDiffusionFFTDirect, cfg, return_field)
+    (the periodic operator); real=True: the real-scalar library."""
+    return _run("AdvectionDiffusionFFTDirect", cfg, return_field, real)
 
 
 def StructuredContext(n_x, n_y, n_z, a_x, a_y, a_z, nu, dt, delta_x, delta_y, delta_z, FFT_MAT: Mat

@@ -20,7 +20,7 @@ import threading
 import numpy as np
 
 from ._lib import CirculantError
-from ._lib_ext import AIJInfo
+from ._lib_ext import AdvDiffConfig, AdvDiffResult, AIJInfo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libcirculant_fft_real.so")
@@ -49,10 +49,40 @@ class StructuredTransportContext(ctypes.Structure):
                 ("FFT_MAT", ctypes.c_void_p)]
 
 
+class FFTPrecDiffusionContext(ctypes.Structure):
+    """struct FFTPrecDiffusionContext (include/diffusion_equation.h) with PetscScalar = double: the
+    transport context's 12 members in order, then mu_x, mu_y, mu_z."""
+    _fields_ = FFTPrecTransportContext._fields_ + [("mu_x", ctypes.c_double), ("mu_y", ctypes.c_double),
+                                                   ("mu_z", ctypes.c_double)]
+
+
+class StructuredDiffusionContext(ctypes.Structure):
+    """struct StructuredDiffusionContext (include/diffusion_equation.h) with PetscScalar = double
+    (passed by value)."""
+    _fields_ = [("n_x", ctypes.c_int64), ("n_y", ctypes.c_int64), ("n_z", ctypes.c_int64),
+                ("a_x", ctypes.c_double), ("a_y", ctypes.c_double), ("a_z", ctypes.c_double), ("nu", ctypes.c_double),
+                ("dt", ctypes.c_double), ("delta_x", ctypes.c_double), ("delta_y", ctypes.c_double),
+                ("delta_z", ctypes.c_double), ("FFT_MAT", ctypes.c_void_p)]
+
+
 def _declare(L) -> None:
     vp, i64, c_int, d = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
     P = ctypes.POINTER
     sig = {
+        # the real plan behind an FFT matrix (include/circulant_fft_real.h)
+        "cfp_rplan_mid_kernel": ([vp, P(c_int)], c_int),
+        # advection-diffusion (include/diffusion_equation.h), PetscScalar = double
+        "getFFTPrec3DDiffusionContext": ([i64, d, i64, i64, i64, d, d, d, d, P(d), P(d),
+                                          P(FFTPrecDiffusionContext)], c_int),
+        "setupFFTPrec3DDiffusion": ([vp], c_int),
+        "applyFFT3DPrecDiffusion": ([vp, vp, vp], c_int),
+        "destroyFFTPrec3DDiffusion": ([vp], c_int),
+        "PetscFft3DDiffusionSolver": ([StructuredDiffusionContext, vp, vp], c_int),
+        "cfp_advdiff_csr": ([i64, i64, i64, P(d), d, P(d), d, c_int, d, P(i64), P(i64), P(d), P(i64)], c_int),
+        "computeAdvectionDiffusionMatrixCartesianAIJ": ([c_int, i64, i64, i64, P(d), d, P(d), d, i64, P(vp)], c_int),
+        "cfp_advdiff_config_default": ([P(AdvDiffConfig), i64], None),
+        "AdvectionDiffusionGMRES": ([P(AdvDiffConfig), P(AdvDiffResult), P(d)], c_int),
+        "AdvectionDiffusionFFTDirect": ([P(AdvDiffConfig), P(AdvDiffResult), P(d)], c_int),
         "PetscErrorLastMessage": ([], ctypes.c_char_p),
         "VecCreateSeq": ([c_int, i64, P(vp)], c_int),
         "VecCreateSeqHIP": ([c_int, i64, P(vp)], c_int),
@@ -341,15 +371,45 @@ def mat_destroy(M) -> None:
         PetscCall(lib().MatDestroy(ctypes.byref(M)))
 
 
-def pc_shell(ctx: FFTPrecTransportContext) -> ctypes.c_void_p:
-    """PCSHELL registered as ToDo.md:1 intends: context + setup / apply / destroy callbacks."""
+def pc_shell(ctx) -> ctypes.c_void_p:
+    """PCSHELL registered as ToDo.md:1 intends: context + setup / apply / destroy callbacks.  An
+    FFTPrecTransportContext takes the transport trio, an FFTPrecDiffusionContext the diffusion one
+    (include/diffusion_equation.h)."""
+    trio = (("setupFFTPrec3DDiffusion", "applyFFT3DPrecDiffusion", "destroyFFTPrec3DDiffusion")
+            if isinstance(ctx, FFTPrecDiffusionContext)
+            else ("setupFFTPrec3D", "applyFFT3DPrecTransport", "destroyFFTPrec3D"))
     pc = ctypes.c_void_p()
     L = lib()
     PetscCall(L.PCCreate(PETSC_COMM_WORLD, ctypes.byref(pc)))
     PetscCall(L.PCSetType(pc, b"shell"))
     PetscCall(L.PCShellSetContext(pc, ctypes.addressof(ctx)))
-    PetscCall(L.PCShellSetSetUp(pc, fn("setupFFTPrec3D")))
-    PetscCall(L.PCShellSetApply(pc, fn("applyFFT3DPrecTransport")))
-    PetscCall(L.PCShellSetDestroy(pc, fn("destroyFFTPrec3D")))
+    PetscCall(L.PCShellSetSetUp(pc, fn(trio[0])))
+    PetscCall(L.PCShellSetApply(pc, fn(trio[1])))
+    PetscCall(L.PCShellSetDestroy(pc, fn(trio[2])))
     PetscCall(L.PCSetUp(pc))
     return pc
+
+
+def diffusion_context(ndim: int, dt: float, dims, a, nu: float, mins, maxs) -> FFTPrecDiffusionContext:
+    """getFFTPrec3DDiffusionContext: the matched numbers lambda_d = a_d dt / h_d, mu_d = nu dt / h_d^2."""
+    ctx = FFTPrecDiffusionContext()
+    d3 = ctypes.c_double * 3
+    PetscCall(lib().getFFTPrec3DDiffusionContext(int(ndim), float(dt), int(dims[0]), int(dims[1]), int(dims[2]),
+                                                 float(a[0]), float(a[1]), float(a[2]), float(nu),
+                                                 d3(*[float(v) for v in mins]), d3(*[float(v) for v in maxs]),
+                                                 ctypes.byref(ctx)))
+    return ctx
+
+
+def mat_real_plan_mid_kernel(A) -> str:
+    """The half-spectrum middle kernel of the real plan behind an FFT matrix (MatFFTHIPGetRealPlan,
+    cfp_rplan_mid_kernel): 'fft', 'zrec2', or 'none' where the real plan lacks the grid."""
+    h = ctypes.c_void_p()
+    PetscCall(lib().MatFFTHIPGetRealPlan(A, ctypes.byref(h)))
+    if not h.value:
+        return "none"
+    k = ctypes.c_int()
+    rc = lib().cfp_rplan_mid_kernel(h, ctypes.byref(k))
+    if rc:
+        raise CirculantError(rc, "cfp_rplan_mid_kernel")
+    return "zrec2" if k.value == 2 else "fft"

@@ -383,8 +383,15 @@ def build_diag_3d(diag: torch.Tensor, cx_hat: torch.Tensor, cy_hat: torch.Tensor
 
 class RealPlan:
     """Real-data apply (include/circulant_fft_real.h): x = C^{-1} b for a
-    real float64 b and a real transport symbol, r2c / half spectrum / c2r, ~80 N bytes per
-    apply.  The reference's real-scalar solve_3D (src/FftLinearSolver_3D.c:6-78, 166-190)."""
+    real float64 b and a real symbol, r2c / half spectrum / c2r, ~80 N bytes per apply (3 sweeps,
+    ~32 N, at 128^3 and 256^3).  The reference's real-scalar solve_3D
+    (src/FftLinearSolver_3D.c:6-78, 166-190).
+
+    Symbols: set_transport_symbol(lam) or set_advdiff_symbol(lam, mu), both with real numbers (a
+    Hermitian symbol, so x is real).  At 256^3 the advection-diffusion symbol's half-spectrum
+    middle sweep solves z by the two-sided recurrence instead of transforming it where both z
+    ratios are <= 1 - 2^-7 (set_mid_kernel('fft') keeps the FFT kernel); mid_kernel() tells what
+    the next apply launches."""
 
     def __init__(self, dims: Sequence[int], device: int | None = None):
         nx, ny, nz = (int(d) for d in dims)
@@ -401,6 +408,41 @@ class RealPlan:
             raise ValueError("lambda must have three real entries")
         check(lib().cfp_rplan_set_symbol_transport(self._h, (ctypes.c_double * 3)(*vals)))
         return self
+
+    @staticmethod
+    def _real3(vals: Sequence, name: str):
+        out = []
+        for v in vals:
+            c = complex(v)
+            if c.imag != 0.0:
+                raise ValueError(f"{name} must be real (got {v!r}): the real plan needs a Hermitian symbol")
+            out.append(c.real)
+        if len(out) != 3:
+            raise ValueError(f"{name} must have three real entries")
+        return (ctypes.c_double * 3)(*out)
+
+    def set_advdiff_symbol(self, lam: Sequence, mu: Sequence) -> "RealPlan":
+        """Diag = 1 + sum_d [lambda_d (1 - w_d) + mu_d (2 - w_d - conj(w_d))] for real lambda_d =
+        a_d dt / h_d and mu_d = nu dt / h_d^2 (CirculantPlan.set_advdiff_symbol's closed form)."""
+        check(lib().cfp_rplan_set_symbol_advdiff(self._h, self._real3(lam, "lambda"), self._real3(mu, "mu")))
+        return self
+
+    MID_KERNELS = {"auto": 0, "fft": 1, "rec": 2}
+
+    def set_mid_kernel(self, mid: str | int) -> "RealPlan":
+        """'auto' (the measured default: the recurrence where eligible), 'fft' (the FFT middle kernel
+        always) or 'rec' (the two-sided z recurrence where the symbol and the grid admit it, else
+        the FFT kernel)."""
+        v = self.MID_KERNELS[mid] if isinstance(mid, str) else int(mid)
+        check(lib().cfp_rplan_set_mid_kernel(self._h, v))
+        return self
+
+    def mid_kernel(self) -> str:
+        """What the next apply launches on the half spectrum: 'zrec2' (256^3, 3 sweeps, an
+        advection-diffusion symbol with mu_z != 0 and both z ratios <= 1 - 2^-7, selected) or 'fft'."""
+        k = ctypes.c_int()
+        check(lib().cfp_rplan_mid_kernel(self._h, ctypes.byref(k)))
+        return "zrec2" if k.value == 2 else "fft"
 
     SCHEDULES = {"auto": 0, "five": 1, "three": 2, "three_alt": 3}
 

@@ -17,6 +17,11 @@
  * At 256^3 the default is a 3-sweep schedule (cfp_three_pass.hip): r2c rows + the 32-point y1
  * DFT of a four-step y split | y2 + z + divide + inverse on the half spectrum | y1 inverse + c2r
  * rows, ~32 N bytes per apply.
+ *
+ * Two symbols: the transport symbol and the advection-diffusion symbol (real lambda and mu, a
+ * Hermitian symbol: for real b the solution is real).  Both run every schedule; at 256^3 the
+ * advection-diffusion symbol's middle sweep can also run as a two-sided z recurrence
+ * (cfp_rplan_set_mid_kernel).
  */
 #ifndef CFP_CIRCULANT_FFT_REAL_H
 #define CFP_CIRCULANT_FFT_REAL_H
@@ -32,6 +37,10 @@ int cfp_rplan_create(cfp_rplan_t *plan, int64_t nx, int64_t ny, int64_t nz, int 
 int cfp_rplan_destroy(cfp_rplan_t plan);
 /* real lambda_x, lambda_y, lambda_z of the transport symbol 1 + sum_d lambda_d (1 - e^{-i theta_d}) */
 int cfp_rplan_set_symbol_transport(cfp_rplan_t plan, const double lam[3]);
+/* the advection-diffusion symbol 1 + sum_d [lambda_d (1 - w_d) + mu_d (2 - w_d - conj(w_d))],
+ * w_d = e^{-i theta_d}, for real lambda_d = a_d dt / h_d and mu_d = nu dt / h_d^2: the closed form
+ * of cfp_plan_set_symbol_advdiff (circulant_fft.h); mu = 0 gives the transport setter's tables */
+int cfp_rplan_set_symbol_advdiff(cfp_rplan_t plan, const double lam[3], const double mu[3]);
 /* x = C^{-1} b for real b (nx*ny*nz doubles on the device); x may alias b */
 int cfp_rplan_apply(cfp_rplan_t plan, const double *b, double *x, void *stream);
 /* schedule: CFP_RSCHEDULE_AUTO (3 sweeps at 128^3 and 256^3, else r2c + 3 half-spectrum passes + c2r),
@@ -45,6 +54,17 @@ int cfp_rplan_apply(cfp_rplan_t plan, const double *b, double *x, void *stream);
 int cfp_rplan_set_schedule(cfp_rplan_t plan, int schedule);
 /* *three = 1 when the next apply runs the 3-sweep schedule */
 int cfp_rplan_schedule(cfp_rplan_t plan, int *three);
+/* The half-spectrum middle sweep of the 3-sweep schedule at 256^3.  For an advection-diffusion
+ * symbol with mu_z != 0 whose two z ratios (cfp_advdiff_z_ratio) are <= 1 - 2^-7 it can solve z by
+ * the two-sided recurrence of the complex plan (CFP_MID_KERNEL_ZREC2) instead of transforming it. */
+#define CFP_RMID_AUTO 0 /* the measured default: the recurrence where eligible (DESIGN.md "256^3 real P2") */
+#define CFP_RMID_FFT 1  /* the FFT middle kernel always */
+#define CFP_RMID_REC 2  /* the recurrence where the symbol and the grid admit it, else the FFT kernel */
+int cfp_rplan_set_mid_kernel(cfp_rplan_t plan, int mid);
+/* what the next apply launches on the half spectrum: CFP_MID_KERNEL_FFT or CFP_MID_KERNEL_ZREC2
+ * (circulant_fft.h); FFT under the 5-pass schedule, at 128^3, for the transport setter, for
+ * mu_z = 0 and over the ratio cap */
+int cfp_rplan_mid_kernel(cfp_rplan_t plan, int *kind);
 /* launches of one apply and their mean duration (ms) over `iters` applies */
 int cfp_rplan_num_passes(cfp_rplan_t plan, int *passes);
 int cfp_rplan_time_passes(cfp_rplan_t plan, const double *b, double *x, int iters, double *ms_out, void *stream);

@@ -19,7 +19,14 @@
  *   PCSetType(pc, PCSHELL); PCShellSetContext(pc, &ctx);
  *   PCShellSetSetUp(pc, setupFFTPrec3DDiffusion); PCShellSetApply(pc, applyFFT3DPrecDiffusion);
  *   PCShellSetDestroy(pc, destroyFFTPrec3DDiffusion);
- * One rank only: on a communicator of several ranks setupFFTPrec3DDiffusion returns PETSC_ERR_SUP.
+ * One rank only, in both builds: on a communicator of several ranks setupFFTPrec3DDiffusion
+ * returns PETSC_ERR_SUP.
+ *
+ * Both scalar builds export every name below.  With real scalars (-DCFP_REAL_SCALAR,
+ * libcirculant_fft_real.so) Vecs and U_out hold doubles, Diag and b_hat are the r2c half spectrum
+ * [nz][ny][nx/2 + 1] (include/pcshell_fft3d.h), and the symbol is set on the real-data plan
+ * (cfp_rplan_set_symbol_advdiff, include/circulant_fft_real.h) as well as on the complex plan that
+ * serves the grids the real plan lacks and an explicit Diag.
  */
 #ifndef CFP_DIFFUSION_EQUATION_H
 #define CFP_DIFFUSION_EQUATION_H
@@ -155,7 +162,8 @@ void cfp_advdiff_config_default(cfp_advdiff_config *cfg, int64_t n);
  * ||U^{n+1} - U^n|| >= precision one KSPSolve of (I + dt L) U^{n+1} = U^n with the stand-in
  * GMRES and PCNONE or the diffusion PCSHELL (MatMult, PCApply and the dots as separate sweeps:
  * the 7-point stencil is not x-local, so there is no fused step).  U_out (optional): the final
- * field, N interleaved (re, im) values.  One rank. */
+ * field, N PetscScalars (interleaved (re, im) values; N doubles in the real-scalar build).  One
+ * rank. */
 PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config *cfg, cfp_advdiff_result *res, double *U_out);
 /* The direct-solver loop: each step is one PetscFft3DDiffusionSolver(ctx, Un, Un), i.e. the
  * periodic operator whatever cfg->bc says.  res: steps, dt, time, last_norm_dU, solve_seconds,

@@ -5,6 +5,8 @@
   python tools/ab_sched.py 256 real:three real:three_alt     # RealPlan schedules on the real part of b
   python tools/ab_sched.py 256 three:0,default three:0,swap64pf --lam 0.6 0.15 0.6 --mu 0.2 0.2 2.5
                                                              # the advection-diffusion symbol: zrec2 against fft
+  python tools/ab_sched.py 256 real:three,fft real:three,rec --lam 0 0 0 --mu 0.3 0.3 1000
+                                                             # the same on the real plan's half spectrum
 
 Every variant applies the same b (SplitMix64 U[-1,1) complex, the bench's transport symbol) in
 place on the current stream, timed with HIP events over `--iters` back-to-back applies; the
@@ -30,7 +32,8 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--lam", type=float, nargs=3, default=[0.6, 0.15, 0.02])
     ap.add_argument("--mu", type=float, nargs=3, default=None,
-                    help="diffusion numbers: the complex plans take set_advdiff_symbol(lam, mu)")
+                    help="diffusion numbers: every plan takes set_advdiff_symbol(lam, mu); a real variant's "
+                         "suffix picks its middle kernel (real:three,rec / real:three,fft / real:three,auto)")
     ap.add_argument("--lib", default=None, help="another build of libcirculant_fft.so (A/B of two builds)")
     args = ap.parse_args()
     if args.lib:
@@ -46,8 +49,14 @@ def main() -> int:
     for v in args.variants:
         if v.startswith("real:"):
             p = cp.RealPlan(n)
-            p.set_transport_symbol(tuple(args.lam))
-            p.set_schedule(v[5:])
+            if args.mu is not None:
+                p.set_advdiff_symbol(tuple(args.lam), tuple(args.mu))
+            else:
+                p.set_transport_symbol(tuple(args.lam))
+            sched, _, mid = v[5:].partition(",")
+            p.set_schedule(sched)
+            if mid:
+                p.set_mid_kernel(mid)
             plans.append(p)
             continue
         p = cp.CirculantPlan(n)
@@ -67,6 +76,7 @@ def main() -> int:
         real = v.startswith("real:")
         res[v] = {"rates": [], "rel_diff": None}
         if real:
+            res[v]["mid_kernel"] = p.mid_kernel()
             res[v]["stage_ms"] = [round(t, 4) for t in p.time_passes(br, torch.empty_like(br), iters=20)]
         else:
             res[v]["passes"] = [q["mode"] for q in p.passes()]
