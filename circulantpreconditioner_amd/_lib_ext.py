@@ -99,7 +99,8 @@ class AdvDiffResult(ctypes.Structure):
                 ("pc_seconds", ctypes.c_double), ("pc_calls", ctypes.c_int64), ("setup_seconds", ctypes.c_double),
                 ("lambda_", ctypes.c_double * 3), ("mu_", ctypes.c_double * 3), ("loop_seconds", ctypes.c_double),
                 ("dev_ms_", ctypes.c_double * 4), ("dev_launches_", ctypes.c_int64 * 4),
-                ("fused_dots", ctypes.c_int64), ("fused_norms", ctypes.c_int64)]
+                ("fused_dots", ctypes.c_int64), ("fused_norms", ctypes.c_int64),
+                ("rstart", ctypes.c_int64), ("nlocal", ctypes.c_int64)]
 
     def as_dict(self) -> dict:
         d = {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_")}
@@ -208,6 +209,13 @@ def declare(L) -> None:
         "cfp_dist_plan_pieces": ([vp, P(c_int)], c_int),
         "cfp_group_set_pieces": ([vp, c_int], c_int),
         "cfp_dist_plan_use_diag": ([vp, c_int], c_int),
+        "cfp_dist_plan_set_symbol_advdiff": ([vp, dp, dp], c_int),
+        "cfp_dist_plan_set_mid_kernel": ([vp, c_int], c_int),
+        "cfp_dist_plan_mid_kernel": ([vp, P(c_int)], c_int),
+        "cfp_group_set_symbol_advdiff": ([vp, dp, dp], c_int),
+        "cfp_group_set_mid_kernel": ([vp, c_int], c_int),
+        "cfp_group_mid_kernel": ([vp, P(c_int)], c_int),
+        "cfp_slab_advdiff_z_table": ([c_int, c_int, dp, dp, dp], c_int),
         # PETSc stand-in: communicators and distributed objects
         "MPI_Comm_size": ([c_int, P(c_int)], c_int),
         "MPI_Comm_rank": ([c_int, P(c_int)], c_int),

@@ -291,6 +291,42 @@ hipError_t launch_repack(const cd* in, cd* out, const SlabLayout& L, i64 planes,
   return hipGetLastError();
 }
 
+enum { SYM_TRANSPORT = 1, SYM_ADVDIFF = 2 };
+
+// the 256^3 slab recurrence: P | 32, P <= 16 (three_pass_slab_supported at 256^3)
+bool slab_rec2_ranks(int P) { return P >= 1 && P <= 16 && 32 % P == 0; }
+
+// Rank r's column table of k_tp_mid_rec2 on its z-pencil block [256 z][256 / P][256 x]
+// (advdiff_z_table's layout [unit][a, r = 256 / beta, b][lane]): 32 (32 / P) units, unit u lane
+// x + 8 y2 holding kx = 8 (u % 32) + x, ky = k1_off + u / 32 + 32 brev3(y2), k1_off = r 32 / P
+std::vector<cd> slab_z_table(int P, int r, const std::vector<cd>& sx, const std::vector<cd>& sy,
+                             std::complex<double> lz, std::complex<double> mz) {
+  const std::complex<double> p = lz + mz, q = mz;
+  const int nk1 = 32 / P, k1_off = r * nk1, units = 32 * nk1;
+  std::vector<cd> t((size_t)units * 3 * 64);
+  for (int u = 0; u < units; ++u)
+    for (int lane = 0; lane < 64; ++lane) {
+      const int x = lane & 7, y2 = lane >> 3;
+      const int k2 = ((y2 & 1) << 2) | (y2 & 2) | (y2 >> 2);
+      const std::complex<double> be =
+          advdiff_z_beta(sx[(size_t)(8 * (u % 32) + x)], sy[(size_t)(k1_off + u / 32 + 32 * k2)], p, q);
+      const std::complex<double> a = p / be, b = q / be, rr = 256.0 / be;
+      t[(size_t)((3 * u) * 64 + lane)] = make_cd(a.real(), a.imag());
+      t[(size_t)((3 * u + 1) * 64 + lane)] = make_cd(rr.real(), rr.imag());
+      t[(size_t)((3 * u + 2) * 64 + lane)] = make_cd(b.real(), b.imag());
+    }
+  return t;
+}
+
+// CFP_SLAB_MID_AUTO: the rank counts at which the recurrence replaces the FFT middle kernel, i.e.
+// where it is faster by more than the spread inside one process.  Measured on one MI355X, rank 0
+// of P, the two kernels alternating over 6 rounds of 2000 sweeps, three symbols
+// (tools/slab_local_timing.py --mid fft rec, profiles/r13_slab_zrec2_ab.txt), FFT -> recurrence
+// in us: P = 1 118.4-119.1 -> 92.3-93.6, P = 2 62.8-63.4 -> 47.3-47.6, P = 4 33.8-34.6 ->
+// 26.4-26.6, P = 8 (128 units, one per workgroup) 25.2-25.4 -> 18.2-18.7, P = 16 (64 units)
+// 23.6-23.7 -> 16.9-17.0; spread inside a kernel <= 2.5 %.  So: every supported P.
+bool slab_rec2_auto(int P) { return slab_rec2_ranks(P); }
+
 // Per-rank device state shared by every executor.
 struct SlabRank {
   SlabLayout L;
@@ -307,7 +343,15 @@ struct SlabRank {
   bool diag = false;      // explicit Diag set (cfp_dist_plan_set_diag)
   int schedule = CFP_SCHEDULE_AUTO;
   int pieces_req = 0;     // 0 = AUTO
+  // the closed form that is set (sym): its kind and numbers, so that set_steps refills its tables
+  int sym_kind = SYM_TRANSPORT;
   double lam_[6] = {0, 0, 0, 0, 0, 0};
+  double mu_[6] = {0, 0, 0, 0, 0, 0};
+  // the advection-diffusion symbol on the 256^3 3-sweep schedule with mu_z != 0 and both z ratios
+  // of the full grid under the cap: this rank's column table of k_tp_mid_rec2 (slab_z_table)
+  cd* zrec2_tab = nullptr;
+  bool zrec2_ok = false;
+  int mid = CFP_SLAB_MID_AUTO;  // cfp_dist_plan_set_mid_kernel
   std::vector<Step> steps;       // the apply
   std::vector<Step> diag_steps;  // the apply with the explicit Diag
 
@@ -349,7 +393,17 @@ struct SlabRank {
           int rc = ensure_tw(s.pass.n);
           if (rc) return rc;
         }
-    return sym ? set_transport(lam_) : CFP_SUCCESS;  // the new schedule's symbol tables
+    return sym ? refill() : CFP_SUCCESS;  // the new schedule's symbol tables
+  }
+  int refill() { return sym_kind == SYM_ADVDIFF ? set_advdiff(lam_, mu_) : set_transport(lam_); }
+  // what the next apply's 3-sweep stage 1 launches: the recurrence (AUTO: slab_rec2_auto)
+  bool use_rec2() const {
+    return three() && zrec2_ok && mid != CFP_SLAB_MID_FFT && (mid == CFP_SLAB_MID_REC || slab_rec2_auto(L.P));
+  }
+  void drop_zrec2() {
+    zrec2_ok = false;
+    if (zrec2_tab) hipFree(zrec2_tab);
+    zrec2_tab = nullptr;
   }
   void release() {
     for (auto& kv : tw) hipFree(kv.second);
@@ -360,20 +414,70 @@ struct SlabRank {
     if (work && own_work) hipFree(work);
     if (work2 && own_work2) hipFree(work2);
     if (diag_t) hipFree(diag_t);
+    drop_zrec2();
     colsym = colsym3 = axsym = work = work2 = diag_t = nullptr;
   }
-  // colsym over the z-pass columns g = ix + nx*iyl (global ky = y0 + iyl); axsym over kz
+  // one axis' part of the transport symbol, lambda (1 - e^{-2 pi i k / n})
+  static std::vector<cd> transport_axis(i64 n, double lr, double li) {
+    const std::vector<cd> hat = host_transport_symbol(n);
+    std::vector<cd> s(hat.size());
+    for (size_t k = 0; k < hat.size(); ++k) {
+      const double cr = hat[k].x, ci = hat[k].y;
+      s[k] = make_cd(cr * lr - ci * li, cr * li + ci * lr);
+    }
+    return s;
+  }
   int set_transport(const double lam[6]) {
-    std::vector<cd> hat[3] = {host_transport_symbol(L.nx), host_transport_symbol(L.ny), host_transport_symbol(L.nz)};
+    const i64 n[3] = {L.nx, L.ny, L.nz};
+    std::vector<cd> s[3];
+    for (int a = 0; a < 3; ++a) s[a] = transport_axis(n[a], lam[2 * a], lam[2 * a + 1]);
+    int rc = upload_tables(s);
+    if (rc) return rc;
+    drop_zrec2();
+    std::memmove(lam_, lam, sizeof(lam_));
+    std::memset(mu_, 0, sizeof(mu_));
+    sym_kind = SYM_TRANSPORT;
+    sym = true;
+    return CFP_SUCCESS;
+  }
+  // The advection-diffusion symbol (cfp_plan_set_symbol_advdiff's): the same tables from
+  // host_advdiff_symbol per axis.  An axis with mu = 0 takes the transport product itself, so
+  // mu = 0 writes the transport setter's bytes.
+  int set_advdiff(const double lam[6], const double mu[6]) {
+    const i64 n[3] = {L.nx, L.ny, L.nz};
     std::vector<cd> s[3];
     for (int a = 0; a < 3; ++a) {
-      const double lr = lam[2 * a], li = lam[2 * a + 1];
-      s[a].resize(hat[a].size());
-      for (size_t k = 0; k < hat[a].size(); ++k) {
-        const double cr = hat[a][k].x, ci = hat[a][k].y;
-        s[a][k] = make_cd(cr * lr - ci * li, cr * li + ci * lr);
-      }
+      if (mu[2 * a] == 0.0 && mu[2 * a + 1] == 0.0) s[a] = transport_axis(n[a], lam[2 * a], lam[2 * a + 1]);
+      else s[a] = host_advdiff_symbol(n[a], {lam[2 * a], lam[2 * a + 1]}, {mu[2 * a], mu[2 * a + 1]});
     }
+    int rc = upload_tables(s);
+    if (rc) return rc;
+    // the 256^3 middle sweep by recurrence: decided on the whole grid's columns, so every rank
+    // decides the same way; the table holds this rank's k1 rows only
+    const std::complex<double> lz(lam[4], lam[5]), mz(mu[4], mu[5]);
+    bool ok = three() && L.nx == 256 && mz != 0.0;
+    if (ok) {
+      double r[2];
+      advdiff_z_ratio(s[0], s[1], lz, mz, r);
+      ok = r[0] <= kZrec2MaxRatio && r[1] <= kZrec2MaxRatio;
+    }
+    if (ok) {
+      const std::vector<cd> t = slab_z_table(L.P, L.r, s[0], s[1], lz, mz);
+      if (!zrec2_tab) HIPCHK(hipMalloc(&zrec2_tab, sizeof(cd) * t.size()));  // (hipMalloc: 256-byte aligned)
+      HIPCHK(hipMemcpy(zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
+      zrec2_ok = true;
+    } else {
+      drop_zrec2();
+    }
+    std::memmove(lam_, lam, sizeof(lam_));
+    std::memmove(mu_, mu, sizeof(mu_));
+    sym_kind = SYM_ADVDIFF;
+    sym = true;
+    return CFP_SUCCESS;
+  }
+  // s: the axes' parts of a separable symbol.  colsym over the z-pass columns g = ix + nx*iyl
+  // (global ky = y0 + iyl); axsym over kz
+  int upload_tables(const std::vector<cd> s[3]) {
     const i64 ncols = L.nx * L.nyl;  // 0 on a rank past the last y row (padded layouts)
     std::vector<cd> col((size_t)(ncols > 0 ? ncols : 1));
     for (i64 g = 0; g < ncols; ++g) {
@@ -392,8 +496,6 @@ struct SlabRank {
       if (!colsym3) HIPCHK(hipMalloc(&colsym3, sizeof(cd) * g.size()));
       HIPCHK(hipMemcpy(colsym3, g.data(), sizeof(cd) * g.size(), hipMemcpyHostToDevice));
     }
-    std::memcpy(lam_, lam, sizeof(lam_));
-    sym = true;
     return CFP_SUCCESS;
   }
   // buffers the steps of `list` touch must exist
@@ -424,7 +526,8 @@ struct SlabRank {
       a.lnyl = ilog2_exact(L.nyp);  // (the 3-sweep slab schedule is never padded: P | 32)
       a.chunk = L.chunk;
       a.k1_off = (int)(L.r * (L.nyp / three_pass_slab_n2(L.nx)));  // N2 rows per k1
-      hipError_t e = launch_three_pass_slab(s.tp, (int)L.nx, in, out, a, s.planes, st);
+      hipError_t e = s.tp == 1 && use_rec2() ? launch_three_pass_slab_rec2(out, a, zrec2_tab, st)
+                                              : launch_three_pass_slab(s.tp, (int)L.nx, in, out, a, s.planes, st);
       return e == hipSuccess ? CFP_SUCCESS : hip_error(e, "slab 3-sweep launch");
     }
     if (s.kind == K_REPACK) {
@@ -806,6 +909,46 @@ extern "C" int cfp_dist_plan_set_symbol_transport(cfp_dist_plan_t p, const doubl
   return p->R.set_transport(lam);
 }
 
+extern "C" int cfp_dist_plan_set_symbol_advdiff(cfp_dist_plan_t p, const double lam[6], const double mu[6]) {
+  if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  HIPCHK(hipSetDevice(p->R.device));
+  return p->R.set_advdiff(lam, mu);
+}
+
+static int mid_check(int mode) {
+  if (mode != CFP_SLAB_MID_AUTO && mode != CFP_SLAB_MID_FFT && mode != CFP_SLAB_MID_REC)
+    return set_error(CFP_ERR_ARG_OUTOFRANGE, "mid kernel must be CFP_SLAB_MID_AUTO, _FFT or _REC");
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_dist_plan_set_mid_kernel(cfp_dist_plan_t p, int mode) {
+  if (!p) return set_error(CFP_ERR_ARG_NULL, "NULL plan");
+  int rc = mid_check(mode);
+  if (rc) return rc;
+  p->R.mid = mode;
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_dist_plan_mid_kernel(cfp_dist_plan_t p, int* kind) {
+  if (!p || !kind) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  *kind = !p->R.diag && p->R.use_rec2() ? CFP_MID_KERNEL_ZREC2 : CFP_MID_KERNEL_FFT;
+  return CFP_SUCCESS;
+}
+
+// Host-only: rank `rank`'s 256^3 recurrence table as (re, im) doubles, 32 (32 / nranks) units of
+// 3 x 64 values (slab_z_table)
+extern "C" int cfp_slab_advdiff_z_table(int nranks, int rank, const double lam[6], const double mu[6], double* out) {
+  if (!lam || !mu || !out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  if (!slab_rec2_ranks(nranks))
+    return set_error(CFP_ERR_ARG_OUTOFRANGE, "the 256^3 slab recurrence needs nranks | 32 and nranks <= 16 (got %d)", nranks);
+  if (rank < 0 || rank >= nranks) return set_error(CFP_ERR_ARG_OUTOFRANGE, "rank %d of %d", rank, nranks);
+  const std::vector<cd> sx = host_advdiff_symbol(256, {lam[0], lam[1]}, {mu[0], mu[1]});
+  const std::vector<cd> sy = host_advdiff_symbol(256, {lam[2], lam[3]}, {mu[2], mu[3]});
+  const std::vector<cd> t = slab_z_table(nranks, rank, sx, sy, {lam[4], lam[5]}, {mu[4], mu[5]});
+  std::memcpy(out, t.data(), sizeof(cd) * t.size());
+  return CFP_SUCCESS;
+}
+
 extern "C" int cfp_dist_plan_local_size(cfp_dist_plan_t p, int64_t* n) {
   if (!p || !n) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
   *n = p->R.L.local;
@@ -1130,6 +1273,31 @@ extern "C" int cfp_group_set_symbol_transport(cfp_group_t g, const double lam[6]
     int rc = R.set_transport(lam);
     if (rc) return rc;
   }
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_group_set_symbol_advdiff(cfp_group_t g, const double lam[6], const double mu[6]) {
+  if (!g || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  for (auto& R : g->R) {
+    HIPCHK(hipSetDevice(R.device));
+    int rc = R.set_advdiff(lam, mu);
+    if (rc) return rc;
+  }
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_group_set_mid_kernel(cfp_group_t g, int mode) {
+  if (!g) return set_error(CFP_ERR_ARG_NULL, "NULL group");
+  int rc = mid_check(mode);
+  if (rc) return rc;
+  for (auto& R : g->R) R.mid = mode;
+  return CFP_SUCCESS;
+}
+
+// every rank decides the same way (the ratios of the whole grid): rank 0's answer
+extern "C" int cfp_group_mid_kernel(cfp_group_t g, int* kind) {
+  if (!g || !kind) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  *kind = g->R[0].use_rec2() ? CFP_MID_KERNEL_ZREC2 : CFP_MID_KERNEL_FFT;
   return CFP_SUCCESS;
 }
 

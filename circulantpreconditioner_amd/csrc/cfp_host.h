@@ -17,6 +17,7 @@ std::vector<cd> host_transport_symbol(i64 n);
 // the advection-diffusion symbol's 1-D parts and the factors of its two-sided z recurrence
 // (cfp_plan.hip; the real plan builds its half-spectrum tables from the same functions)
 std::vector<cd> host_advdiff_symbol(i64 n, std::complex<double> lam, std::complex<double> mu);
+std::complex<double> advdiff_z_beta(cd x, cd y, std::complex<double> p, std::complex<double> q);
 void advdiff_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz,
                      std::complex<double> mz, double ratios[2]);
 std::vector<cd> advdiff_z_table(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz,

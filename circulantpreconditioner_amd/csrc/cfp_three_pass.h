@@ -103,6 +103,13 @@ hipError_t launch_three_pass(int stage, int n, const cd* in, cd* out, const TPAr
 bool three_pass_slab_supported(const i64 n[3], int P);
 int three_pass_slab_n2(i64 n);  // rows y2 per k1 of the four-step y split (8 at 256, 16 at 512)
 hipError_t launch_three_pass_slab(int stage, int n, const cd* in, cd* out, const TPArgs& a, int nzl, hipStream_t s);
+// stage 1 of a 256^3 z-slab rank for the advection-diffusion symbol: the two-sided z recurrence
+// (launch_three_pass_rec2's kernels) on [256][nyl][256] in place, a.lnyl and a.k1_off as for the
+// FFT stage.  tab2 (device, 16-byte aligned): 32 nyl / 8 units of launch_three_pass_rec2's layout,
+// unit u holding kx = 8 (u % 32) + x, ky = a.k1_off + u / 32 + 32 brev3(y2); the caller has checked
+// both z ratios on the whole grid.  A data pointer that is only 8-byte aligned takes the
+// non-prefetching kernel.
+hipError_t launch_three_pass_slab_rec2(cd* data, const TPArgs& a, const cd* tab2, hipStream_t s);
 // real-data plan at n^3, n = 128 or 256 (cfp_real.hip): stage 0 P1r (b -> H, Q), 1 P2 on H
 // (n/2 x n x n, in place), 3 the same on the Nyquist column Q (n x n, kx = n/2, in place;
 // a.colsym = its [ky] symbol), 2 P3r (H, Q -> x, x a.scale); a.tw = W_n, a.colsym =

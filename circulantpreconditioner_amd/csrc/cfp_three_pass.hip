@@ -2319,4 +2319,20 @@ hipError_t launch_three_pass_real_rec2(cd* H, const TPArgs& a, const cd* tab2, h
   return hipGetLastError();
 }
 
+// Stage 1 of a z-slab rank at 256^3 by the two-sided recurrence: launch_three_pass_rec2's kernels
+// (no instantiation of its own) on the rank's [256 z][nyl][256 x] block.  Units: 32 x tiles times
+// the nyl / 8 local k1 rows, so with 8 or 16 ranks (128 or 64 units) every workgroup has one unit
+// and runs the body's last-unit instantiation alone: one table fetch, no prefetch of a next unit.
+hipError_t launch_three_pass_slab_rec2(cd* data, const TPArgs& a, const cd* tab2, hipStream_t s) {
+  const int nk1 = a.lnyl ? (1 << a.lnyl) / 8 : 32;  // local k1 values: nyl / N2
+  const int units = 32 * nk1;
+  if (nk1 < 1 || nk1 > 32 || a.k1_off < 0 || a.k1_off + nk1 > 32) return hipErrorInvalidValue;
+  const dim3 g(grid_of(units, 1)), b(1024);
+  if (((uintptr_t)data & 15) == 0)  // the LDS-DMA prefetch takes 16-byte addresses
+    hipLaunchKernelGGL((k_tp_mid_rec2<0, true, kP2LoadFlags>), g, b, 0, s, data, a, units, tab2);
+  else
+    hipLaunchKernelGGL((k_tp_mid_rec2<0, false, kP2LoadFlags>), g, b, 0, s, data, a, units, tab2);
+  return hipGetLastError();
+}
+
 }  // namespace cfp

@@ -48,8 +48,7 @@ void pack6(PetscScalar x, PetscScalar y, PetscScalar z, double out[6]) {
 // Use (or refresh) the plan's advection-diffusion symbol for these numbers; equal numbers on an
 // untouched plan reuse it (as ensure_transport_symbol, pcshell_fft3d.cpp)
 PetscErrorCode ensure_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6]) {
-  PetscCheck(s->plan && !s->slab.plan, PETSC_COMM_SELF, PETSC_ERR_SUP,
-             "the advection-diffusion symbol is set on a one-rank FFT matrix only");
+  PetscCheck(s->plan || s->slab.plan, PETSC_COMM_SELF, PETSC_ERR_ARG_WRONGSTATE, "the FFT matrix has no plan");
   double ad[12];
   std::memcpy(ad, lam, 6 * sizeof(double));
   std::memcpy(ad + 6, mu, 6 * sizeof(double));
@@ -178,9 +177,8 @@ extern "C" PetscErrorCode setupFFTPrec3DDiffusion(PC pc) {
   PetscCheck(ctx, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "setupFFTPrec3DDiffusion: no context attached to the PC");
   PetscCheck(ctx->n_x >= 1 && ctx->n_y >= 1 && ctx->n_z >= 1, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE,
              "setupFFTPrec3DDiffusion: n_x, n_y, n_z must be >= 1");
-  int P = 1;
-  PetscCallMPI(MPI_Comm_size(PETSC_COMM_WORLD, &P));
-  PetscCheck(P == 1, PETSC_COMM_SELF, PETSC_ERR_SUP, "setupFFTPrec3DDiffusion: one rank only");
+  // several ranks: this rank's z slab (MatCreateFFTHIP refuses a split that does not divide n_z
+  // with PETSC_ERR_ARG_SIZ), Diag and the work vectors its z-planes
   const PetscInt dims[3] = {ctx->n_z, ctx->n_y, ctx->n_x};
   PetscCall(MatCreateFFTHIP(PETSC_COMM_WORLD, 3, dims, &ctx->FFT_MAT));
   PetscCall(MatCreateVecsFFTW(ctx->FFT_MAT, NULL, &ctx->Diag, NULL));
@@ -285,9 +283,6 @@ extern "C" PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config* cfg,
   PetscCheck(cfg->pc == CFP_ADVDIFF_PC_NONE || cfg->on_device, PETSC_COMM_SELF, PETSC_ERR_SUP,
              "the FFT preconditioner runs on HIP vectors only");
   PetscCheck(cfg->dt > 0 && cfg->nu >= 0, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, "dt must be > 0 and nu >= 0");
-  int P = 1;
-  PetscCallMPI(MPI_Comm_size(PETSC_COMM_WORLD, &P));
-  PetscCheck(P == 1, PETSC_COMM_SELF, PETSC_ERR_SUP, "AdvectionDiffusionGMRES: one rank only");
   std::memset((void*)res, 0, sizeof(*res));
   const double t_setup = wall();
   const PetscInt nx = cfg->nx, ny = cfg->ny, nz = cfg->nz, N = nx * ny * nz;
@@ -298,11 +293,21 @@ extern "C" PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config* cfg,
   const double dt = cfg->dt;
   res->dt = dt;
 
+  // one rank: sequential Vecs and AIJ; several (PETSC_COMM_WORLD of PetscMiniSetCommWorld):
+  // distributed ones in PETSC_DECIDE rows, as TransportEquationGMRES
+  int P = 1;
+  PetscCallMPI(MPI_Comm_size(PETSC_COMM_WORLD, &P));
   Vec Un, dUn;
-  PetscCall(cfp_driver::create_state(cfg, 1, &Un, &dUn));
+  PetscCall(cfp_driver::create_state(cfg, P, &Un, &dUn));
+  PetscInt lo, nloc;
+  PetscCall(VecGetOwnershipRange(Un, &lo, NULL));
+  PetscCall(VecGetLocalSize(Un, &nloc));
+  res->rstart = lo;
+  res->nlocal = nloc;
 
   Mat A;
-  PetscCall(computeAdvectionDiffusionMatrixCartesianAIJ(PETSC_COMM_SELF, nx, ny, nz, h, dt, cfg->a, cfg->nu, cfg->bc, &A));
+  PetscCall(computeAdvectionDiffusionMatrixCartesianAIJ(P > 1 ? PETSC_COMM_WORLD : PETSC_COMM_SELF, nx, ny, nz, h, dt,
+                                                        cfg->a, cfg->nu, cfg->bc, &A));
   PetscCall(MatShift(A, 1.0));
 
   KSP ksp;
@@ -332,7 +337,7 @@ extern "C" PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config* cfg,
   PetscCall(cfp_driver::gmres_setup(ksp, A, Un, dUn, cfg->on_device, t_setup, res));
 
   PetscCall(cfp_driver::gmres_time_loop(ksp, Un, dUn, dt, cfg, res));
-  PetscCall(cfp_driver::copy_out(Un, N, U_out));
+  PetscCall(cfp_driver::copy_out(Un, nloc, U_out));
   PetscCall(KSPDestroy(&ksp));  // destroys the PC, whose destroy callback frees setup's objects
   PetscCall(MatDestroy(&A));
   PetscCall(VecDestroy(&Un));
@@ -359,8 +364,18 @@ extern "C" PetscErrorCode AdvectionDiffusionFFTDirect(const cfp_advdiff_config* 
     res->lambda[d] = n[d] > 1 ? cfg->a[d] * dt / h[d] : 0.0;
     res->mu[d] = n[d] > 1 ? cfg->nu * dt / (h[d] * h[d]) : 0.0;
   }
+  // several ranks: distributed Vecs in PETSC_DECIDE rows (whole z-planes: P | nz) on the slab-backed matrix
+  int P = 1;
+  PetscCallMPI(MPI_Comm_size(PETSC_COMM_WORLD, &P));
+  PetscCheck(nz % P == 0, PETSC_COMM_SELF, PETSC_ERR_ARG_SIZ,
+             "AdvectionDiffusionFFTDirect: the number of ranks must divide nz (whole z-planes per rank)");
   Vec Un, dUn;
-  PetscCall(cfp_driver::create_state(cfg, 1, &Un, &dUn));
+  PetscCall(cfp_driver::create_state(cfg, P, &Un, &dUn));
+  PetscInt lo, nloc;
+  PetscCall(VecGetOwnershipRange(Un, &lo, NULL));
+  PetscCall(VecGetLocalSize(Un, &nloc));
+  res->rstart = lo;
+  res->nlocal = nloc;
   Mat FFT_MAT;
   const PetscInt dims[3] = {nz, ny, nx};
   PetscCall(MatCreateFFT(PETSC_COMM_WORLD, 3, dims, MATFFTW, &FFT_MAT));
@@ -370,7 +385,7 @@ extern "C" PetscErrorCode AdvectionDiffusionFFTDirect(const cfp_advdiff_config* 
 
   const auto solve = [&](Vec U) { return PetscFft3DDiffusionSolver(ctx, U, U); };
   PetscCall(cfp_driver::direct_time_loop(Un, dUn, dt, cfg, solve, res));
-  PetscCall(cfp_driver::copy_out(Un, N, U_out));
+  PetscCall(cfp_driver::copy_out(Un, nloc, U_out));
   PetscCall(MatDestroy(&FFT_MAT));
   PetscCall(VecDestroy(&Un));
   PetscCall(VecDestroy(&dUn));

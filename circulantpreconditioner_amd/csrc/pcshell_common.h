@@ -272,11 +272,13 @@ CFP_INTERNAL PetscErrorCode pc_fused_ba(PC pc, FFTPrecTransportContext* ctx, Mat
 // X = C^{-1} b with the plan's own symbol, whatever set it (one apply of FFT_MAT's plan; b may
 // be X) -- the diffusion direct solver
 CFP_INTERNAL PetscErrorCode own_symbol_apply(Mat FFT_MAT, Vec X, Vec b);
-// The two build-specific pieces of the diffusion boundary (diffusion_cartesian.cpp), one rank.
+// The two build-specific pieces of the diffusion boundary (diffusion_cartesian.cpp).
 // pc_set_advdiff_symbol: the advection-diffusion symbol of lam[6], mu[6] (re, im per axis) on
-// every plan behind the matrix (the real build: its complex plan and its real plan, real parts).
-// pc_advdiff_diag: Diag := that symbol in the build's spectral layout (complex: the full grid;
-// real: the half spectrum [nz][ny][nx/2 + 1]), remembered as the plan's own (remember_diag).
+// every plan behind the matrix (the real build: its complex plan and its real plan, real parts;
+// several ranks, both builds: slab.plan, with dist_version moved on).
+// pc_advdiff_diag: Diag := this rank's z-planes of that symbol in the build's spectral layout
+// (complex: [nzl][ny][nx]; real: the half spectrum [nzl][ny][nx/2 + 1]), remembered as the plan's
+// own (remember_diag).
 CFP_INTERNAL PetscErrorCode pc_set_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6]);
 CFP_INTERNAL PetscErrorCode pc_advdiff_diag(ShellBase* s, Vec Diag, const double lam[6], const double mu[6]);
 

@@ -347,14 +347,39 @@ PetscErrorCode cfp_pc::own_symbol_apply(Mat FFT_MAT, Vec X, Vec b) {
 // the diffusion boundary's build-specific pieces (pcshell_common.h): one complex plan; Diag is the
 // plan's own closed-form symbol on the full grid
 PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6]) {
-  CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
+  if (s->slab.plan) {  // several ranks: this rank's z slab
+    CFPCALL(cfp_dist_plan_set_symbol_advdiff(s->slab.plan, lam, mu));
+    ++s->dist_version;
+  } else {
+    CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
+  }
   return PETSC_SUCCESS;
 }
-PetscErrorCode cfp_pc::pc_advdiff_diag(ShellBase* s, Vec Diag, const double*, const double*) {
+PetscErrorCode cfp_pc::pc_advdiff_diag(ShellBase* s, Vec Diag, const double lam[6], const double mu[6]) {
   DevOut d;
   PetscCall(d.get(Diag, s->nl));
-  int rc = cfp_plan_get_diag(s->plan, d.ptr(), nullptr);
-  if (rc == CFP_SUCCESS) rc = cfp_stream_sync(nullptr);
+  int rc = CFP_SUCCESS;
+  if (s->slab.plan) {  // this rank's z-planes [nzl][ny][nx] of the closed form, from the axes' parts
+    const PetscInt nx = s->dims[0], ny = s->dims[1];
+    std::vector<double> c[3];
+    for (int a = 0; a < 3 && !rc; ++a) {
+      c[a].resize(2 * (size_t)s->dims[a]);
+      rc = cfp_advdiff_symbol_1d(s->dims[a], lam + 2 * a, mu + 2 * a, c[a].data());
+    }
+    std::vector<double> h(2 * (size_t)s->nl);
+    for (PetscInt kz = s->z0; kz < s->z0 + s->nzl && !rc; ++kz)
+      for (PetscInt ky = 0; ky < ny; ++ky)
+        for (PetscInt kx = 0; kx < nx; ++kx) {
+          const size_t i = 2 * (size_t)(((kz - s->z0) * ny + ky) * nx + kx);
+          h[i] = 1.0 + c[0][2 * kx] + c[1][2 * ky] + c[2][2 * kz];
+          h[i + 1] = c[0][2 * kx + 1] + c[1][2 * ky + 1] + c[2][2 * kz + 1];
+        }
+    if (!rc && hipMemcpy(d.ptr(), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
+      rc = CFP_ERR_LIB;
+  } else {
+    rc = cfp_plan_get_diag(s->plan, d.ptr(), nullptr);
+    if (rc == CFP_SUCCESS) rc = cfp_stream_sync(nullptr);
+  }
   PetscCall(d.put());
   CFPCALL(rc);
   PetscCall(s->remember_diag(Diag));

@@ -350,6 +350,11 @@ PetscErrorCode cfp_pc::own_symbol_apply(Mat FFT_MAT, Vec X, Vec b) {
 // caller (ensure_advdiff_symbol) then records ad / ad_version, which rplan_current reads.
 PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* base, const double lam[6], const double mu[6]) {
   RShell* s = static_cast<RShell*>(base);
+  if (s->slab.plan) {  // several ranks: the complex slab plan on the promoted slab, as the transport apply
+    CFPCALL(cfp_dist_plan_set_symbol_advdiff(s->slab.plan, lam, mu));
+    ++s->dist_version;
+    return PETSC_SUCCESS;
+  }
   CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
   const double l3[3] = {lam[0], lam[2], lam[4]}, m3[3] = {mu[0], mu[2], mu[4]};
   if (s->rplan) CFPCALL(cfp_rplan_set_symbol_advdiff(s->rplan, l3, m3));

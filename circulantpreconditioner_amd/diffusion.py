@@ -113,13 +113,16 @@ def _run(name: str, cfg: AdvDiffConfig, return_field: bool, real: bool):
     else:
         PetscCall(getattr(lib(), name)(ctypes.byref(cfg), ctypes.byref(res), ptr))
     d = res.as_dict()
+    if out is not None:  # this rank's rows (all of them on one rank)
+        out = out[:d["nlocal"]].copy()
     return (d, out) if return_field else d
 
 
 def run(cfg: AdvDiffConfig, return_field: bool = False, real: bool = False):
     """AdvectionDiffusionGMRES: the implicit time loop with the stand-in GMRES and PCNONE or the
     diffusion PCSHELL; returns the result dict (and the final field when asked: N complex values,
-    or N doubles with real=True, the real-scalar library)."""
+    or N doubles with real=True, the real-scalar library).  When PETSC_COMM_WORLD has several ranks
+    (petsc.set_comm_world) the field is this rank's rows res['rstart'] .. + res['nlocal']."""
     return _run("AdvectionDiffusionGMRES", cfg, return_field, real)
 
 
@@ -127,6 +130,33 @@ def run_direct(cfg: AdvDiffConfig, return_field: bool = False, real: bool = Fals
     """AdvectionDiffusionFFTDirect: one PetscFft3DDiffusionSolver(ctx, Un, Un) per implicit step
     (the periodic operator); real=True: the real-scalar library."""
     return _run("AdvectionDiffusionFFTDirect", cfg, return_field, real)
+
+
+def context(ndim: int, dt: float, dims: Sequence[int], a: Sequence[float], nu: float, mins, maxs):
+    """getFFTPrec3DDiffusionContext: the PCSHELL context with the matched numbers
+    lambda_d = a_d dt / h_d, mu_d = nu dt / h_d^2."""
+    from ._lib_ext import FFTPrecDiffusionContext
+    ctx = FFTPrecDiffusionContext()
+    S = PetscScalar.of
+    PetscCall(lib().getFFTPrec3DDiffusionContext(int(ndim), S(dt), int(dims[0]), int(dims[1]), int(dims[2]),
+                                                 S(a[0]), S(a[1]), S(a[2]), S(nu), _d3(mins), _d3(maxs),
+                                                 ctypes.byref(ctx)))
+    return ctx
+
+
+def pc_shell(ctx):
+    """A PC of type PCSHELL with the diffusion callbacks registered on ctx (setupFFTPrec3DDiffusion,
+    applyFFT3DPrecDiffusion, destroyFFTPrec3DDiffusion) and set up.  On PETSC_COMM_WORLD of several
+    ranks the FFT matrix is this rank's z slab and ctx.Diag its z-planes of the symbol."""
+    from .petsc import PC, _fn
+    pc = PC()
+    PetscCall(lib().PCSetType(pc.h, b"shell"))
+    pc.ctx = ctx
+    PetscCall(lib().PCShellSetContext(pc.h, ctypes.addressof(ctx)))
+    PetscCall(lib().PCShellSetSetUp(pc.h, _fn("setupFFTPrec3DDiffusion")))
+    PetscCall(lib().PCShellSetApply(pc.h, _fn("applyFFT3DPrecDiffusion")))
+    PetscCall(lib().PCShellSetDestroy(pc.h, _fn("destroyFFTPrec3DDiffusion")))
+    return pc.setup()
 
 
 def StructuredContext(n_x, n_y, n_z, a_x, a_y, a_z, nu, dt, delta_x, delta_y, delta_z, FFT_MAT: Mat

@@ -27,6 +27,24 @@ def _slab_schedule(schedule) -> int:
     return {"auto": 0, "five": 1, "three": 2}[schedule] if isinstance(schedule, str) else int(schedule)
 
 
+def _mid_kernel(mid) -> int:
+    """'auto' | 'fft' | 'rec' (CFP_SLAB_MID_AUTO / _FFT / _REC)"""
+    return {"auto": 0, "fft": 1, "rec": 2}[mid] if isinstance(mid, str) else int(mid)
+
+
+def slab_advdiff_z_table(nranks: int, rank: int, lam, mu):
+    """Host-only: rank `rank`'s table of the 256^3 slab recurrence, a complex array
+    [32 * (32 // nranks)][3: a, r = 256 / beta, b][64 lanes] (cfp_slab_advdiff_z_table)."""
+    import numpy as np
+    if int(nranks) < 1 or 32 % int(nranks) or int(nranks) > 16:
+        units = 1  # the library rejects the split; it writes nothing
+    else:
+        units = 32 * (32 // int(nranks))
+    out = np.empty((units, 3, 64), dtype=np.complex128)
+    check(lib().cfp_slab_advdiff_z_table(int(nranks), int(rank), _lam6(lam), _lam6(mu), out.ctypes.data))
+    return out
+
+
 def slab_layout(dims: Sequence[int], nranks: int, rank: int) -> dict:
     """Host-only layout query (no GPU needed).  ny_local: this rank's z-pencil rows (blocks of
     ny_chunk = ceil(ny / nranks), FFTW-MPI's split; the last ranks may hold fewer);
@@ -159,6 +177,24 @@ class SlabPlan:
     def set_transport_symbol(self, lam) -> "SlabPlan":
         check(lib().cfp_dist_plan_set_symbol_transport(self._h, _lam6(lam)))
         return self
+
+    def set_advdiff_symbol(self, lam, mu) -> "SlabPlan":
+        """The advection-diffusion symbol (CirculantPlan.set_advdiff_symbol's closed form); mu = 0
+        writes exactly the transport setter's tables."""
+        check(lib().cfp_dist_plan_set_symbol_advdiff(self._h, _lam6(lam), _lam6(mu)))
+        return self
+
+    def set_mid_kernel(self, mid: str | int) -> "SlabPlan":
+        """Middle kernel of the 256^3 3-sweep schedule: 'auto' (the measured default), 'fft', or
+        'rec' (the two-sided z recurrence wherever the symbol admits it)."""
+        check(lib().cfp_dist_plan_set_mid_kernel(self._h, _mid_kernel(mid)))
+        return self
+
+    def mid_kernel(self) -> str:
+        """What the next apply launches as the middle kernel: 'fft' or 'zrec2'."""
+        k = ctypes.c_int()
+        check(lib().cfp_dist_plan_mid_kernel(self._h, ctypes.byref(k)))
+        return "zrec2" if k.value == 2 else "fft"
 
     def set_schedule(self, schedule: str | int) -> "SlabPlan":
         """Local passes: 'auto' (3 sweeps at 256^3 and 512^3 with world | 32, world <= 16), 'five' or 'three'."""
@@ -337,6 +373,22 @@ class SlabGroup:
     def set_transport_symbol(self, lam) -> "SlabGroup":
         check(lib().cfp_group_set_symbol_transport(self._h, _lam6(lam)))
         return self
+
+    def set_advdiff_symbol(self, lam, mu) -> "SlabGroup":
+        """As SlabPlan.set_advdiff_symbol, on every slab."""
+        check(lib().cfp_group_set_symbol_advdiff(self._h, _lam6(lam), _lam6(mu)))
+        return self
+
+    def set_mid_kernel(self, mid: str | int) -> "SlabGroup":
+        """As SlabPlan.set_mid_kernel: 'auto' | 'fft' | 'rec'."""
+        check(lib().cfp_group_set_mid_kernel(self._h, _mid_kernel(mid)))
+        return self
+
+    def mid_kernel(self) -> str:
+        """'fft' or 'zrec2' (every slab decides the same way)."""
+        k = ctypes.c_int()
+        check(lib().cfp_group_mid_kernel(self._h, ctypes.byref(k)))
+        return "zrec2" if k.value == 2 else "fft"
 
     def set_schedule(self, schedule: str | int) -> "SlabGroup":
         """Local passes per slab: 'auto' (3 sweeps at 256^3 and 512^3 with P | 32, P <= 16), 'five' or 'three'."""

@@ -141,6 +141,27 @@ int cfp_dist_plan_num_steps(cfp_dist_plan_t plan, int *nsteps);
 int cfp_dist_plan_step(cfp_dist_plan_t plan, int step, int64_t *desc);
 int cfp_dist_plan_run_step(cfp_dist_plan_t plan, int step, const double *b_dev, double *x_dev, void *stream);
 int cfp_dist_plan_set_symbol_transport(cfp_dist_plan_t plan, const double lam[6]);
+/* The advection-diffusion symbol of cfp_plan_set_symbol_advdiff (circulant_fft.h),
+ * 1 + sum_d [lam_d (1 - w_d) + mu_d (2 - w_d - conj w_d)], lam and mu as (re, im) per axis.
+ * mu = 0 writes exactly the tables of cfp_dist_plan_set_symbol_transport.  The plan remembers the
+ * closed form that was set last: a new schedule or piece count refills its tables, and
+ * cfp_dist_plan_clear_diag / cfp_dist_plan_use_diag(plan, 0) return to it. */
+int cfp_dist_plan_set_symbol_advdiff(cfp_dist_plan_t plan, const double lam[6], const double mu[6]);
+/* Middle kernel of the 3-sweep schedule at 256^3.  With the advection-diffusion symbol, mu_z != 0
+ * and both z ratios of the whole grid (cfp_advdiff_z_ratio) <= 1 - 2^-7, the rank's z-pencil block
+ * may take the two-sided z recurrence of the one-GPU plan (CFP_MID_KERNEL_ZREC2) instead of the
+ * FFT kernel; every rank decides the same way.  The semantics are cfp_rplan_set_mid_kernel's. */
+#define CFP_SLAB_MID_AUTO 0 /* the measured default: the recurrence where eligible, at every nranks (DESIGN.md "256^3 slab P2") */
+#define CFP_SLAB_MID_FFT 1  /* the FFT middle kernel always */
+#define CFP_SLAB_MID_REC 2  /* the recurrence wherever it is eligible, else the FFT kernel */
+int cfp_dist_plan_set_mid_kernel(cfp_dist_plan_t plan, int mode);
+/* what the next apply launches: CFP_MID_KERNEL_FFT or CFP_MID_KERNEL_ZREC2 */
+int cfp_dist_plan_mid_kernel(cfp_dist_plan_t plan, int *kind);
+/* Host-only, no GPU: rank `rank`'s table of that recurrence at 256^3 as (re, im) doubles,
+ * [unit][a, r = 256 / beta, b][lane] with 32 (32 / nranks) units of 64 lanes: unit u, lane
+ * x + 8 y2 holds the column kx = 8 (u % 32) + x, ky = rank 32 / nranks + u / 32 + 32 brev3(y2).
+ * CFP_ERR_ARG_OUTOFRANGE unless nranks | 32 and nranks <= 16. */
+int cfp_slab_advdiff_z_table(int nranks, int rank, const double lam[6], const double mu[6], double *out_host);
 /* Explicit Diag: this rank's natural slab of it (local_size values, device).  A collective
  * (every rank calls it): the Diag is moved once into the z-pencil layout of the fused z pass,
  * and later applies divide by it until cfp_dist_plan_clear_diag.  (solve_3D with a Diag Vec.) */
@@ -183,6 +204,9 @@ int cfp_dist_plan_pieces(cfp_dist_plan_t plan, int *pieces);
 int cfp_group_create(cfp_group_t *group, int64_t nx, int64_t ny, int64_t nz, int nranks, const int *devices);
 int cfp_group_destroy(cfp_group_t group);
 int cfp_group_set_symbol_transport(cfp_group_t group, const double lam[6]);
+int cfp_group_set_symbol_advdiff(cfp_group_t group, const double lam[6], const double mu[6]); /* as cfp_dist_plan_* */
+int cfp_group_set_mid_kernel(cfp_group_t group, int mode);
+int cfp_group_mid_kernel(cfp_group_t group, int *kind);
 /* b_devs[r], x_devs[r]: slab r on devices[r]; synchronous */
 int cfp_group_apply(cfp_group_t group, const double *const *b_devs, double *const *x_devs);
 int cfp_group_set_schedule(cfp_group_t group, int schedule); /* as cfp_dist_plan_set_schedule */

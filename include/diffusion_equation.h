@@ -19,14 +19,18 @@
  *   PCSetType(pc, PCSHELL); PCShellSetContext(pc, &ctx);
  *   PCShellSetSetUp(pc, setupFFTPrec3DDiffusion); PCShellSetApply(pc, applyFFT3DPrecDiffusion);
  *   PCShellSetDestroy(pc, destroyFFTPrec3DDiffusion);
- * One rank only, in both builds: on a communicator of several ranks setupFFTPrec3DDiffusion
- * returns PETSC_ERR_SUP.
+ * On PETSC_COMM_WORLD of P ranks (P | n_z) the FFT matrix is this rank's z slab
+ * (include/circulant_fft_dist.h), every Vec holds the rank's z-planes and Diag is the rank's
+ * planes of the symbol, as with the transport PCSHELL; a split with P not dividing n_z returns
+ * PETSC_ERR_ARG_SIZ.
  *
  * Both scalar builds export every name below.  With real scalars (-DCFP_REAL_SCALAR,
  * libcirculant_fft_real.so) Vecs and U_out hold doubles, Diag and b_hat are the r2c half spectrum
  * [nz][ny][nx/2 + 1] (include/pcshell_fft3d.h), and the symbol is set on the real-data plan
  * (cfp_rplan_set_symbol_advdiff, include/circulant_fft_real.h) as well as on the complex plan that
- * serves the grids the real plan lacks and an explicit Diag.
+ * serves the grids the real plan lacks and an explicit Diag.  On several ranks the real build
+ * promotes to the complex slab plan, as its transport apply does, and Diag is the rank's planes
+ * [nzl][ny][nx/2 + 1] of the half spectrum.
  */
 #ifndef CFP_DIFFUSION_EQUATION_H
 #define CFP_DIFFUSION_EQUATION_H
@@ -92,7 +96,8 @@ PetscErrorCode applyFFT3DPrecDiffusion(PC pc, Vec b, Vec x);
 PetscErrorCode destroyFFTPrec3DDiffusion(PC pc);
 
 /* ---- direct solver: x = (I + dt L_periodic)^{-1} b with customCtx.FFT_MAT from MatCreateFFT
- * (one rank); b may be x.  The symbol is set once per (lambda, mu) and kept between calls. */
+ * (on PETSC_COMM_WORLD of several ranks: the slab-backed matrix, b and x the rank's z-planes); b
+ * may be x.  The symbol is set once per (lambda, mu) and kept between calls. */
 PetscErrorCode PetscFft3DDiffusionSolver(struct StructuredDiffusionContext customCtx, Vec b, Vec x);
 
 /* ---- the operator */
@@ -153,6 +158,7 @@ typedef struct {
   double dev_ms[4];       /* cfg->profile: as cfp_transport_result */
   int64_t dev_launches[4];
   int64_t fused_dots, fused_norms;  /* 0: the 7-point stencil is not x-local, nothing is fused */
+  int64_t rstart, nlocal; /* this rank's rows of the field [rstart, rstart + nlocal) (one rank: all) */
 } cfp_advdiff_result;
 
 /* [-0.5, 0.5]^3, n^3 cells, a = (1, 0, 0), nu = 0.01, dt = 0.01, one step, precision 1e-8, 1000
@@ -162,12 +168,14 @@ void cfp_advdiff_config_default(cfp_advdiff_config *cfg, int64_t n);
  * ||U^{n+1} - U^n|| >= precision one KSPSolve of (I + dt L) U^{n+1} = U^n with the stand-in
  * GMRES and PCNONE or the diffusion PCSHELL (MatMult, PCApply and the dots as separate sweeps:
  * the 7-point stencil is not x-local, so there is no fused step).  U_out (optional): the final
- * field, N PetscScalars (interleaved (re, im) values; N doubles in the real-scalar build).  One
- * rank. */
+ * field, N PetscScalars (interleaved (re, im) values; N doubles in the real-scalar build).  On
+ * PETSC_COMM_WORLD of several ranks (PetscMiniSetCommWorld) the Vecs and the AIJ are distributed in
+ * PETSC_DECIDE rows, as TransportEquationGMRES's: U_out then holds this rank's res->nlocal rows
+ * from res->rstart on. */
 PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config *cfg, cfp_advdiff_result *res, double *U_out);
 /* The direct-solver loop: each step is one PetscFft3DDiffusionSolver(ctx, Un, Un), i.e. the
  * periodic operator whatever cfg->bc says.  res: steps, dt, time, last_norm_dU, solve_seconds,
- * pc_calls, lambda, mu. */
+ * pc_calls, lambda, mu, rstart, nlocal (several ranks: as AdvectionDiffusionGMRES, needs P | nz). */
 PetscErrorCode AdvectionDiffusionFFTDirect(const cfp_advdiff_config *cfg, cfp_advdiff_result *res, double *U_out);
 
 #ifdef __cplusplus
