@@ -57,6 +57,7 @@ def _declare(L) -> None:
         "cfp_rplan_destroy": ([vp], c_int),
         "cfp_rplan_set_symbol_transport": ([vp, P(ctypes.c_double)], c_int),
         "cfp_rplan_set_symbol_advdiff": ([vp, P(ctypes.c_double), P(ctypes.c_double)], c_int),
+        "cfp_rplan_set_symbol_upwind": ([vp, P(ctypes.c_double), P(ctypes.c_double)], c_int),
         "cfp_rplan_set_mid_kernel": ([vp, c_int], c_int),
         "cfp_rplan_mid_kernel": ([vp, P(c_int)], c_int),
         "cfp_rplan_apply": ([vp, vp, vp, vp], c_int),

@@ -157,6 +157,8 @@ def declare(L) -> None:
     sig = {
         "cfp_plan_mid_kernel": ([vp, P(c_int)], c_int), "cfp_transport_z_ratio": ([i64, i64, dp, P(ctypes.c_double)], c_int),
         "cfp_plan_set_symbol_advdiff": ([vp, dp, dp], c_int),
+        "cfp_plan_set_symbol_upwind": ([vp, dp, dp], c_int),
+        "cfp_upwind_to_advdiff": ([dp, dp, dp, dp], c_int),
         "cfp_advdiff_symbol_1d": ([i64, P(ctypes.c_double), P(ctypes.c_double), dp], c_int),
         "cfp_advdiff_z_ratio": ([i64, i64, dp, dp, P(ctypes.c_double)], c_int),
         # slab-distributed plan over RCCL + single-process group
@@ -210,6 +212,8 @@ def declare(L) -> None:
         "cfp_group_set_pieces": ([vp, c_int], c_int),
         "cfp_dist_plan_use_diag": ([vp, c_int], c_int),
         "cfp_dist_plan_set_symbol_advdiff": ([vp, dp, dp], c_int),
+        "cfp_dist_plan_set_symbol_upwind": ([vp, dp, dp], c_int),
+        "cfp_group_set_symbol_upwind": ([vp, dp, dp], c_int),
         "cfp_dist_plan_set_mid_kernel": ([vp, c_int], c_int),
         "cfp_dist_plan_mid_kernel": ([vp, P(c_int)], c_int),
         "cfp_group_set_symbol_advdiff": ([vp, dp, dp], c_int),
@@ -334,6 +338,7 @@ def declare(L) -> None:
         "getFFTPrec3DDiffusionContext": ([i64, S, i64, i64, i64, S, S, S, S, P(ctypes.c_double), P(ctypes.c_double),
                                           P(FFTPrecDiffusionContext)], c_int),
         "setupFFTPrec3DDiffusion": ([vp], c_int),
+        "setupFFTPrec3DDiffusionUpwind": ([vp], c_int),
         "applyFFT3DPrecDiffusion": ([vp, vp, vp], c_int),
         "destroyFFTPrec3DDiffusion": ([vp], c_int),
         "PetscFft3DDiffusionSolver": ([StructuredDiffusionContext, vp, vp], c_int),
@@ -391,6 +396,7 @@ def declare(L) -> None:
         # the reference-named boundary
         "applyFFT3DPrecTransport": ([vp, vp, vp], c_int),
         "setupFFTPrec3D": ([vp], c_int),
+        "setupFFTPrec3DUpwind": ([vp], c_int),
         "destroyFFTPrec3D": ([vp], c_int),
         "getFFTPrec3DContext": ([i64, S, i64, S, S, S, S, S, S, S, S, S, P(FFTPrecTransportContext)], c_int),
         "FFTPrecTransportContextCreate": ([P(vp)], c_int),

@@ -921,6 +921,14 @@ static int mid_check(int mode) {
   return CFP_SUCCESS;
 }
 
+extern "C" int cfp_dist_plan_set_symbol_upwind(cfp_dist_plan_t p, const double lam[6], const double mu[6]) {
+  if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  // the mapped pair is what the rank remembers, so a refill (set_schedule, set_pieces) repeats it
+  double l2[6], m2[6];
+  int rc = cfp_upwind_to_advdiff(lam, mu, l2, m2);
+  return rc ? rc : cfp_dist_plan_set_symbol_advdiff(p, l2, m2);
+}
+
 extern "C" int cfp_dist_plan_set_mid_kernel(cfp_dist_plan_t p, int mode) {
   if (!p) return set_error(CFP_ERR_ARG_NULL, "NULL plan");
   int rc = mid_check(mode);
@@ -1284,6 +1292,13 @@ extern "C" int cfp_group_set_symbol_advdiff(cfp_group_t g, const double lam[6], 
     if (rc) return rc;
   }
   return CFP_SUCCESS;
+}
+
+extern "C" int cfp_group_set_symbol_upwind(cfp_group_t g, const double lam[6], const double mu[6]) {
+  if (!g || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  double l2[6], m2[6];
+  int rc = cfp_upwind_to_advdiff(lam, mu, l2, m2);
+  return rc ? rc : cfp_group_set_symbol_advdiff(g, l2, m2);
 }
 
 extern "C" int cfp_group_set_mid_kernel(cfp_group_t g, int mode) {

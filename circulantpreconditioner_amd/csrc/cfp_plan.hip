@@ -256,6 +256,10 @@ struct cfp_plan_s {
   // advdiff_z_table; allocated with the first eligible symbol)
   bool zrec2_ok = false;
   cd* zrec2_tab = nullptr;
+  // the upwind symbol with Re lamz < 0 and muz == 0 (cfp_plan_set_symbol_upwind only): zrecb_ok =
+  // every column's |q / (1 + s_x + s_y + q)| <= 1 - 2^-13, q = -lamz, so the 256^3 P2 may solve z
+  // by the backward recurrence (k_tp_mid_recb); lamz then holds q.  Any other setter clears it.
+  bool zrecb_ok = false;
   bool external_x = false;  // x transformed by the caller (real plan): y/z passes only, no 1/N
   // long axes (n > 4096): four-step split n = n1 n2, both <= 4096 (0: a short axis).  Their
   // spectrum stays in position order p = m1 + n1 m2 for frequency m = m2 + n2 m1.
@@ -345,6 +349,11 @@ bool use_plane(const cfp_plan_s* p) {
 
 bool plan_zrec2(const cfp_plan_s* p) {
   return p->zrec2_ok && p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
+         three_pass_zrec_shape((int)p->n[0], p->tp_shape);
+}
+
+bool plan_zrecb(const cfp_plan_s* p) {
+  return p->zrecb_ok && p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
          three_pass_zrec_shape((int)p->n[0], p->tp_shape);
 }
 
@@ -574,7 +583,10 @@ int run_apply(cfp_plan_s* p, const cd* diag_override, const cd* b, cd* x, hipStr
           a.zrec = 1;
           a.lamz = p->lamz;
         }
-        if (q.tp == 1 && plan_zrec2(p)) e = launch_three_pass_rec2(tout, a, p->zrec2_tab, s);
+        if (q.tp == 1 && plan_zrecb(p)) {
+          a.lamz = p->lamz;
+          e = launch_three_pass_recb(tout, a, s);
+        } else if (q.tp == 1 && plan_zrec2(p)) e = launch_three_pass_rec2(tout, a, p->zrec2_tab, s);
         else e = launch_three_pass(q.tp, tn, tin, tout, a, p->tp_shape, s);
       }
       g_stamp = LaunchStamp{};
@@ -732,7 +744,7 @@ int set_separable(cfp_plan_s* p, const std::vector<cd> hat[3], const double lam[
     }
   }
   ++p->sym_version;
-  p->zrec_ok = p->zrec2_ok = false;
+  p->zrec_ok = p->zrec2_ok = p->zrecb_ok = false;
   return upload_separable(p, s);
 }
 
@@ -849,7 +861,9 @@ extern "C" int cfp_plan_set_symbol_transport(cfp_plan_t p, const double lam[6]) 
 
 extern "C" int cfp_plan_mid_kernel(cfp_plan_t p, int* kind) {
   if (!p || !kind) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  *kind = plan_zrec(p) ? CFP_MID_KERNEL_ZREC : (plan_zrec2(p) ? CFP_MID_KERNEL_ZREC2 : CFP_MID_KERNEL_FFT);
+  *kind = plan_zrec(p) ? CFP_MID_KERNEL_ZREC
+                       : (plan_zrecb(p) ? CFP_MID_KERNEL_ZREC_BACK
+                                        : (plan_zrec2(p) ? CFP_MID_KERNEL_ZREC2 : CFP_MID_KERNEL_FFT));
   return CFP_SUCCESS;
 }
 
@@ -860,7 +874,7 @@ extern "C" int cfp_plan_set_symbol_advdiff(cfp_plan_t p, const double lam[6], co
   std::vector<cd> s[3];
   for (int a = 0; a < 3; ++a) s[a] = host_advdiff_symbol(p->n[a], lamc(lam, a), lamc(mu, a));
   ++p->sym_version;
-  p->zrec_ok = p->zrec2_ok = false;
+  p->zrec_ok = p->zrec2_ok = p->zrecb_ok = false;
   int rc = upload_separable(p, s);
   if (rc) return rc;
   if (p->n[0] == 256 && p->n[1] == 256 && p->n[2] == 256) {  // the one grid the recurrence kernels are built for
@@ -880,6 +894,42 @@ extern "C" int cfp_plan_set_symbol_advdiff(cfp_plan_t p, const double lam[6], co
         p->zrec2_ok = true;
       }
     }
+  }
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_upwind_to_advdiff(const double lam[6], const double mu[6], double lam_out[6], double mu_out[6]) {
+  if (!lam || !mu || !lam_out || !mu_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  // |lam| (1 - conj w) + mu (2 - w - conj w) = lam (1 - w) + (mu - lam) (2 - w - conj w) for lam < 0
+  for (int a = 0; a < 3; ++a) {
+    const bool neg = lam[2 * a] < 0.0;
+    for (int c = 0; c < 2; ++c) {
+      const double l = lam[2 * a + c], m = mu[2 * a + c];
+      lam_out[2 * a + c] = l;
+      mu_out[2 * a + c] = neg ? m - l : m;
+    }
+  }
+  return CFP_SUCCESS;
+}
+
+extern "C" int cfp_plan_set_symbol_upwind(cfp_plan_t p, const double lam[6], const double mu[6]) {
+  if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  double l2[6], m2[6];
+  cfp_upwind_to_advdiff(lam, mu, l2, m2);
+  // the tables, the version bump, the dropped graphs and the zrec / zrec2 routing of the mapped pair
+  int rc = cfp_plan_set_symbol_advdiff(p, l2, m2);
+  if (rc) return rc;
+  const std::complex<double> lz = lamc(lam, 2), mz = lamc(mu, 2);
+  if (p->n[0] == 256 && p->n[1] == 256 && p->n[2] == 256 && lz.real() < 0.0 && mz == 0.0) {
+    // pure upwind transport against z: first order towards z + 1.  The mapped pair has p = 0 and
+    // q = -lamz, so its ratios (advdiff_z_ratio) are a = 0 and b = q / (c + q): the backward
+    // recurrence under k_tp_mid_rec's cap, else the FFT kernel (never the two-sided one)
+    double r[2];
+    advdiff_z_ratio(p->sym1d[0], p->sym1d[1], lz, -lz, r);
+    p->zrec2_ok = false;
+    p->zrec_amax = r[1];
+    p->zrecb_ok = r[1] <= kZrecMaxRatio;
+    p->lamz = make_cd(-lz.real(), -lz.imag());
   }
   return CFP_SUCCESS;
 }
@@ -934,7 +984,7 @@ extern "C" int cfp_plan_set_diag(cfp_plan_t p, const double* diag, int on_device
   DeviceGuard dg(p->device);
   free_symbol(p);
   ++p->sym_version;
-  p->zrec_ok = p->zrec2_ok = false;
+  p->zrec_ok = p->zrec2_ok = p->zrecb_ok = false;
   HIPCHK(hipMalloc(&p->diag, sizeof(cd) * (size_t)p->N));
   HIPCHK(hipMemcpy(p->diag, diag, sizeof(cd) * (size_t)p->N, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   p->sym_kind = 2;

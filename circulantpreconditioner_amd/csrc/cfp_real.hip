@@ -401,6 +401,18 @@ extern "C" int cfp_rplan_set_symbol_advdiff(cfp_rplan_t p, const double lam[3], 
   return CFP_SUCCESS;
 }
 
+extern "C" int cfp_rplan_set_symbol_upwind(cfp_rplan_t p, const double lam[3], const double mu[3]) {
+  if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  // cfp_upwind_to_advdiff on real numbers; the tables, the routing and what the plan remembers
+  // are the mapped pair's
+  double l2[3], m2[3];
+  for (int a = 0; a < 3; ++a) {
+    l2[a] = lam[a];
+    m2[a] = lam[a] < 0.0 ? mu[a] - lam[a] : mu[a];
+  }
+  return cfp_rplan_set_symbol_advdiff(p, l2, m2);
+}
+
 extern "C" int cfp_rplan_set_mid_kernel(cfp_rplan_t p, int mid) {
   if (!p) return set_error(CFP_ERR_ARG_NULL, "NULL plan");
   if (mid != CFP_RMID_AUTO && mid != CFP_RMID_FFT && mid != CFP_RMID_REC)

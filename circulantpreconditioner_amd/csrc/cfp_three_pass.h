@@ -84,6 +84,10 @@ bool three_pass_zrec_shape(int n, TPShape shape);
 // kx = 8 (u % 32) + x, ky = u / 32 + 32 brev3(y2); the caller has checked both z ratios
 constexpr int kRec2TabLen = 1024 * 3 * 64;
 hipError_t launch_three_pass_rec2(cd* data, const TPArgs& a, const cd* tab2, hipStream_t s);
+// P2 of those shapes for the upwind transport symbol with lambda_z < 0 (cfp_plan_set_symbol_upwind):
+// the backward recurrence u_z = a u_{z+1} + w_z (k_tp_mid_recb, k_tp_mid_rec on the planes in
+// reverse order).  a.lamz = -lambda_z; the caller has checked the ratio |a| <= 1 - 2^-13
+hipError_t launch_three_pass_recb(cd* data, const TPArgs& a, hipStream_t s);
 
 bool three_pass_supported(const i64 n[3]);
 // 100^3 (n = R^2, R = 10: cfp_three_pass_sq.hip); launch_three_pass routes n = 100 there.

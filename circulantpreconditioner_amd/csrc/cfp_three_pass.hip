@@ -20,6 +20,8 @@
 //       registers of the lane that owns the column, one carry per wave)
 //       (k_tp_mid_rec2, the same for an advection-diffusion symbol with mu_z != 0 and both z
 //       ratios <= 1 - 2^-7: a forward and a backward recurrence, two carries per wave)
+//       (k_tp_mid_recb, k_tp_mid_rec on the planes in reverse order: the upwind transport symbol
+//       with lambda_z < 0, the recurrence u_z = a u_{z+1} + w_z; at the end of the file)
 //   P3  k_tp_rows<inv>: P1 on the conjugate, x 1/N
 //
 // P1/P3 workgroups are N1 x 16 threads x 16 points with a split-LDS exchange buffer of
@@ -1136,7 +1138,9 @@ __device__ __forceinline__ void y2_inv_pair(cd& vp, cd& vq, cd w, cd w8, cd w4, 
 // base plus one offset register for all 16 slots, instead of 16 address pairs.  The callers pass
 // opaque copies of u and loff, so that the addresses are formed again at each phase.
 // NX: the row length in points (256; the real plan's half spectrum: 128, with loff on rows of NX).
-template <int NX>
+// ZREV: the planes in reverse order, slot m of wave wv is z = 255 - (16 wv + m) (k_tp_mid_recb):
+// the same 256 planes of the tile, so the same addresses, bounds and 16-byte alignment.
+template <int NX, bool ZREV = false>
 struct TileT {
   static constexpr int TN = 256, N2 = 8, XT = 8, NXT = NX / XT;
   cd* data;
@@ -1144,7 +1148,8 @@ struct TileT {
   int wv;
   double* pf_l;
   __device__ __forceinline__ cd* slot_ptr(int u, int m) const {
-    return data + ((u % NXT) * XT + (i64)NX * N2 * (u / NXT) + zs * (16 * wv + m));
+    if constexpr (ZREV) return data + ((u % NXT) * XT + (i64)NX * N2 * (u / NXT) + zs * (TN - 1 - (16 * wv + m)));
+    else return data + ((u % NXT) * XT + (i64)NX * N2 * (u / NXT) + zs * (16 * wv + m));
   }
   // this wave's slots 0 .. NPF-1 of unit u -> LDS, lane-linear
   template <int NPF, int LD>
@@ -1169,7 +1174,7 @@ struct TileT {
 using Tile = TileT<256>;
 }  // namespace rec
 
-template <int PROBE, bool PF, int LD>
+template <int PROBE, bool PF, int LD, bool ZREV = false>
 __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPArgs& a, int nunits,
                                                 double* __restrict__ pf_l, cd* __restrict__ carr,
                                                 cd* __restrict__ ctab, cd* __restrict__ tw_l) {
@@ -1201,9 +1206,9 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
   if (wv == 0 && (int)blockIdx.x < nunits) ctab_put(0, colsym_of((int)blockIdx.x));
   __syncthreads();
   const unsigned loff = 16u * ((unsigned)x + (unsigned)TN * (unsigned)y2);  // this lane's (x, row y2)
-  const rec::Tile tile{data, zs, wv, pf_l};
+  const rec::TileT<256, ZREV> tile{data, zs, wv, pf_l};
   if constexpr (PF) {
-    if ((int)blockIdx.x < nunits) tile.prefetch<NPF, LD>((int)blockIdx.x, loff);
+    if ((int)blockIdx.x < nunits) tile.template prefetch<NPF, LD>((int)blockIdx.x, loff);
   }
   const cd zero = make_cd(0.0, 0.0);
   // the y2 DFT's per-lane constants (rec::y2_fwd_pair)
@@ -1233,7 +1238,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
         // behind a vmcnt(16) measured 0.7 % slower, profiles/r07_zrec_ab.txt)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int m = 0; m < NPF; ++m) v[m] = tile.prefetched<NPF>(m, idx(lane));
+        for (int m = 0; m < NPF; ++m) v[m] = tile.template prefetched<NPF>(m, idx(lane));
       }
       if constexpr (more) csn = colsym_of(it + (int)gridDim.x);  // every wave loads (no wait at a join), wave 0 uses it
       {
@@ -1241,7 +1246,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
         unsigned lo1 = loff;
         asm volatile("" : "+s"(ul), "+v"(lo1));  // scalar base + this register, formed here
 #pragma unroll
-        for (int m = NPF; m < 16; ++m) v[m] = tile.load<LD>(ul, m, lo1);
+        for (int m = NPF; m < 16; ++m) v[m] = tile.template load<LD>(ul, m, lo1);
       }
     }
     if (more && wv == 0) ctab_put(nbuf, csn);
@@ -1317,7 +1322,7 @@ __device__ __forceinline__ void tp_mid_rec_body(cd* __restrict__ data, const TPA
       // 90.0 us instead of 86.0 (profiles/r08_zrows_probe.txt).  No global load follows it inside
       // the unit, so no wait drains it early.
       if constexpr (PF && more && !(PROBE & PR_NO_LOAD)) {
-        tile.prefetch<NPF, LD>(it + (int)gridDim.x, loff);
+        tile.template prefetch<NPF, LD>(it + (int)gridDim.x, loff);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (!(PROBE & PR_NO_STORE)) {
@@ -2334,5 +2339,50 @@ hipError_t launch_three_pass_slab_rec2(cd* data, const TPArgs& a, const cd* tab2
     hipLaunchKernelGGL((k_tp_mid_rec2<0, false, kP2LoadFlags>), g, b, 0, s, data, a, units, tab2);
   return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// P2 for the upwind transport symbol with lambda_z < 0 (k_tp_mid_recb; 256^3, default shape).  The
+// column's symbol is c + q (1 - e^{+2 pi i kz / nz}), q = -lambda_z: with a = q / (c + q) the z
+// solve is the backward cyclic system u_z = a u_{z+1} + w_z, w = v nz / (c + q), which z -> 255 - z
+// turns into k_tp_mid_rec's forward one.  So the kernel is tp_mid_rec_body on the planes in reverse
+// order (rec::TileT<256, true>: slot m of wave wv is plane 255 - (16 wv + m); wave 15 slot 15 is
+// plane 0, wave 0 slot 0 plane 255, the tile's own 256 planes) with a.lamz = q: the twiddle
+// W^{y2 k1}, the y2 DFT, the column table and the scans do not depend on z.
+// (Kernel and launcher last in the file, as launch_three_pass_real_rec2 above: every other
+// function's assembly stays the parent's, tools/isa_same.py.)
+template <int PROBE = 0, bool PF = false, int LD = 0, int TAG = 0>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4)))
+k_tp_mid_recb(cd* data, TPArgs a, int nunits) {
+#ifndef CFP_KEXP
+  static_assert(PROBE == 0, "timing probes are built in tools/kexp only");
+#endif
+  __shared__ __attribute__((aligned(16))) double pf_l[PF ? 16 * kRecNPF * 128 : 2];
+  __shared__ __attribute__((aligned(16))) cd carr[2 * 16 * 64];
+  __shared__ __attribute__((aligned(16))) cd ctab[3 * 2 * 64];
+  __shared__ cd tw_l[256];
+  tp_mid_rec_body<PROBE, PF, LD, true>(data, a, nunits, pf_l, carr, ctab, tw_l);
+}
+
+// a.lamz = -lambda_z (the caller has checked the ratio's cap); TAG 1 inside the stand-in KSP and
+// the non-prefetching body for an 8-byte-aligned buffer, as launch_mid_rec.
+// Not in the tools/kexp probe builds (CFP_KEXP): a probe's own instantiations are emitted behind
+// this file's, so four more kernels here would renumber their labels; a probe that wants
+// k_tp_mid_recb instantiates it itself.
+#ifndef CFP_KEXP
+hipError_t launch_three_pass_recb(cd* data, const TPArgs& a, hipStream_t s) {
+  constexpr int units = (256 / 8) * (256 / 8);  // x tiles x k1
+  if (a.lnyl != 0 || a.k1_off != 0) return hipErrorInvalidValue;  // one GPU's natural layout only
+  const bool pf = ((uintptr_t)data & 15) == 0;  // the LDS-DMA prefetch takes 16-byte addresses
+  const dim3 g(grid_of(units, 1)), b(1024);
+  if (a.krylov) {
+    if (pf) TP_LAUNCH((k_tp_mid_recb<0, true, kP2LoadFlags, 1>), g, b, s, data, a, units);
+    else TP_LAUNCH((k_tp_mid_recb<0, false, kP2LoadFlags, 1>), g, b, s, data, a, units);
+  } else {
+    if (pf) TP_LAUNCH((k_tp_mid_recb<0, true, kP2LoadFlags>), g, b, s, data, a, units);
+    else TP_LAUNCH((k_tp_mid_recb<0, false, kP2LoadFlags>), g, b, s, data, a, units);
+  }
+  return hipGetLastError();
+}
+#endif  // CFP_KEXP
 
 }  // namespace cfp

@@ -47,16 +47,19 @@ void pack6(PetscScalar x, PetscScalar y, PetscScalar z, double out[6]) {
 
 // Use (or refresh) the plan's advection-diffusion symbol for these numbers; equal numbers on an
 // untouched plan reuse it (as ensure_transport_symbol, pcshell_fft3d.cpp)
-PetscErrorCode ensure_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6]) {
+// (upwind: through the upwind setters, lam of either sign)
+PetscErrorCode ensure_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6], bool upwind = false) {
   PetscCheck(s->plan || s->slab.plan, PETSC_COMM_SELF, PETSC_ERR_ARG_WRONGSTATE, "the FFT matrix has no plan");
   double ad[12];
   std::memcpy(ad, lam, 6 * sizeof(double));
   std::memcpy(ad + 6, mu, 6 * sizeof(double));
-  if (s->has_ad && s->symbol_version() == s->ad_version && std::memcmp(s->ad, ad, sizeof(ad)) == 0)
+  if (s->has_ad && s->ad_upwind == upwind && s->symbol_version() == s->ad_version &&
+      std::memcmp(s->ad, ad, sizeof(ad)) == 0)
     return PETSC_SUCCESS;
-  PetscCall(pc_set_advdiff_symbol(s, lam, mu));
+  PetscCall(pc_set_advdiff_symbol(s, lam, mu, upwind));
   std::memcpy(s->ad, ad, sizeof(ad));
   s->has_ad = true;
+  s->ad_upwind = upwind;
   s->ad_version = s->symbol_version();
   return PETSC_SUCCESS;
 }
@@ -193,6 +196,66 @@ extern "C" PetscErrorCode setupFFTPrec3DDiffusion(PC pc) {
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 
+// The two setups of the upwind symbol (cfp_plan_set_symbol_upwind: a cell coupled to index - 1 or
+// index + 1 by the sign of lambda_d, the operators of cfp_transport_csr with CFP_UPWIND_FIXED and of
+// cfp_advdiff_csr).  ctx: the 12 leading members the two contexts share; Diag is materialised from
+// the advection-diffusion closed form of the mapped numbers (cfp_upwind_to_advdiff) and remembered
+// as the plan's own, so apply, applyBA and destroy are the existing callbacks.
+static PetscErrorCode setup_upwind(PC pc, FFTPrecTransportContext* ctx, const double lam[6], const double mu[6],
+                                   const char* who) {
+  PetscCheck(ctx, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, who);
+  PetscCheck(ctx->n_x >= 1 && ctx->n_y >= 1 && ctx->n_z >= 1, PETSC_COMM_SELF, PETSC_ERR_ARG_OUTOFRANGE, who);
+  const PetscInt dims[3] = {ctx->n_z, ctx->n_y, ctx->n_x};
+  PetscCall(MatCreateFFTHIP(PETSC_COMM_WORLD, 3, dims, &ctx->FFT_MAT));
+  PetscCall(MatCreateVecsFFTW(ctx->FFT_MAT, NULL, &ctx->Diag, NULL));
+  PetscCall(MatCreateVecsFFTW(ctx->FFT_MAT, &ctx->b_cartesien, &ctx->b_hat, NULL));
+  ShellBase* s;
+  PetscCall(shell_base(ctx->FFT_MAT, &s));
+  PetscCall(ensure_advdiff_symbol(s, lam, mu, true));
+  double l2[6], m2[6];
+  CFPCALL(cfp_upwind_to_advdiff(lam, mu, l2, m2));
+  PetscCall(pc_advdiff_diag(s, ctx->Diag, l2, m2));
+#ifndef CFP_REAL_SCALAR
+  // the operator's row-class form for applyFFT3DPrecTransportBA, built now (as setupFFTPrec3D)
+  Mat A = nullptr;
+  PetscCall(PCGetOperators(pc, &A, NULL));
+  MatType mt = nullptr;
+  if (A && !s->slab.plan) PetscCall(MatGetType(A, &mt));
+  if (mt && std::strcmp(mt, MATSEQAIJ) == 0) {
+    PetscBool has, xl;
+    PetscMiniDia dia;
+    PetscCall(PetscMiniMatAIJGetDia(A, ctx->n_x, &has, &xl, &dia));
+  }
+#endif
+  return PETSC_SUCCESS;
+}
+
+extern "C" PetscErrorCode setupFFTPrec3DUpwind(PC pc) {
+  PetscFunctionBeginUser;
+  FFTPrecTransportContext* ctx = nullptr;
+  PetscCall(PCShellGetContext(pc, &ctx));
+  PetscCheck(ctx, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "setupFFTPrec3DUpwind: no context attached to the PC");
+  double lam[6];
+  const double mu[6] = {0, 0, 0, 0, 0, 0};
+  pack6(ctx->lambda_x, ctx->lambda_y, ctx->lambda_z, lam);
+  PetscCall(setup_upwind(pc, ctx, lam, mu, "setupFFTPrec3DUpwind: n_x, n_y, n_z must be >= 1"));
+  PetscFunctionReturn(PETSC_SUCCESS);
+}
+
+extern "C" PetscErrorCode setupFFTPrec3DDiffusionUpwind(PC pc) {
+  PetscFunctionBeginUser;
+  FFTPrecDiffusionContext* ctx = nullptr;
+  PetscCall(PCShellGetContext(pc, &ctx));
+  PetscCheck(ctx, PETSC_COMM_SELF, PETSC_ERR_ARG_NULL, "setupFFTPrec3DDiffusionUpwind: no context attached to the PC");
+  double lam[6], mu[6];
+  pack6(ctx->lambda_x, ctx->lambda_y, ctx->lambda_z, lam);
+  pack6(ctx->mu_x, ctx->mu_y, ctx->mu_z, mu);
+  // (the leading members are FFTPrecTransportContext's, static_assert above)
+  PetscCall(setup_upwind(pc, reinterpret_cast<FFTPrecTransportContext*>(ctx), lam, mu,
+                         "setupFFTPrec3DDiffusionUpwind: n_x, n_y, n_z must be >= 1"));
+  PetscFunctionReturn(PETSC_SUCCESS);
+}
+
 // the plan's own-symbol apply: applyFFT3DPrecTransport's body on the shared leading members
 extern "C" PetscErrorCode applyFFT3DPrecDiffusion(PC pc, Vec b, Vec x) { return applyFFT3DPrecTransport(pc, b, x); }
 extern "C" PetscErrorCode destroyFFTPrec3DDiffusion(PC pc) { return destroyFFTPrec3D(pc); }
@@ -316,15 +379,17 @@ extern "C" PetscErrorCode AdvectionDiffusionGMRES(const cfp_advdiff_config* cfg,
   PetscCall(cfp_driver::gmres_create(cfg, PETSC_FALSE, &ksp, &pc));
   FFTPrecDiffusionContext ctx;
   std::memset((void*)&ctx, 0, sizeof(ctx));
-  if (cfg->pc == CFP_ADVDIFF_PC_FFT) {
+  if (cfg->pc == CFP_ADVDIFF_PC_FFT || cfg->pc == CFP_ADVDIFF_PC_FFT_UPWIND) {
     PetscCall(getFFTPrec3DDiffusionContext(dim, dt, nx, ny, nz, cfg->a[0], cfg->a[1], cfg->a[2], cfg->nu, cfg->xmin,
                                            cfg->xmax, &ctx));
     PetscCall(PCSetType(pc, PCSHELL));
     PetscCall(PCShellSetContext(pc, &ctx));
-    PetscCall(PCShellSetSetUp(pc, setupFFTPrec3DDiffusion));
+    const bool up = cfg->pc == CFP_ADVDIFF_PC_FFT_UPWIND;
+    PetscCall(PCShellSetSetUp(pc, up ? setupFFTPrec3DDiffusionUpwind : setupFFTPrec3DDiffusion));
     PetscCall(PCShellSetApply(pc, applyFFT3DPrecDiffusion));
     PetscCall(PCShellSetDestroy(pc, destroyFFTPrec3DDiffusion));
-    PetscCall(PCShellSetName(pc, "circulant FFT, advection-diffusion (HIP)"));
+    PetscCall(PCShellSetName(pc, up ? "circulant FFT, upwind advection-diffusion (HIP)"
+                                    : "circulant FFT, advection-diffusion (HIP)"));
     res->lambda[0] = std::real(ctx.lambda_x);
     res->lambda[1] = std::real(ctx.lambda_y);
     res->lambda[2] = std::real(ctx.lambda_z);

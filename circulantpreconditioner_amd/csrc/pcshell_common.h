@@ -225,7 +225,10 @@ struct CFP_INTERNAL ShellBase {
   PetscInt fused_ba = 0;                     // applyBA calls that took pc_fused_ba (MatFFTHIPGetFusedBACount)
   // the advection-diffusion numbers (lam[6], mu[6]) the diffusion boundary last set on the plan
   // (diffusion_cartesian.cpp) and the symbol version right after: equal numbers reuse the symbol
+  // ad_upwind: they went through the upwind setter (the numbers kept are the caller's; the same
+  // tables as the advdiff setter with the mapped pair, but a routing of their own)
   bool has_ad = false;
+  bool ad_upwind = false;
   double ad[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t ad_version = 0;
 
@@ -275,11 +278,13 @@ CFP_INTERNAL PetscErrorCode own_symbol_apply(Mat FFT_MAT, Vec X, Vec b);
 // The two build-specific pieces of the diffusion boundary (diffusion_cartesian.cpp).
 // pc_set_advdiff_symbol: the advection-diffusion symbol of lam[6], mu[6] (re, im per axis) on
 // every plan behind the matrix (the real build: its complex plan and its real plan, real parts;
-// several ranks, both builds: slab.plan, with dist_version moved on).
+// several ranks, both builds: slab.plan, with dist_version moved on); upwind: by the upwind setters
+// (cfp_plan_set_symbol_upwind and its siblings) instead, lam of either sign.
 // pc_advdiff_diag: Diag := this rank's z-planes of that symbol in the build's spectral layout
 // (complex: [nzl][ny][nx]; real: the half spectrum [nzl][ny][nx/2 + 1]), remembered as the plan's
 // own (remember_diag).
-CFP_INTERNAL PetscErrorCode pc_set_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6]);
+CFP_INTERNAL PetscErrorCode pc_set_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6],
+                                                  bool upwind = false);
 CFP_INTERNAL PetscErrorCode pc_advdiff_diag(ShellBase* s, Vec Diag, const double lam[6], const double mu[6]);
 
 // defined by pcshell_boundary.cpp

@@ -346,10 +346,13 @@ PetscErrorCode cfp_pc::own_symbol_apply(Mat FFT_MAT, Vec X, Vec b) {
 
 // the diffusion boundary's build-specific pieces (pcshell_common.h): one complex plan; Diag is the
 // plan's own closed-form symbol on the full grid
-PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6]) {
+PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* s, const double lam[6], const double mu[6], bool upwind) {
   if (s->slab.plan) {  // several ranks: this rank's z slab
-    CFPCALL(cfp_dist_plan_set_symbol_advdiff(s->slab.plan, lam, mu));
+    if (upwind) CFPCALL(cfp_dist_plan_set_symbol_upwind(s->slab.plan, lam, mu));
+    else CFPCALL(cfp_dist_plan_set_symbol_advdiff(s->slab.plan, lam, mu));
     ++s->dist_version;
+  } else if (upwind) {
+    CFPCALL(cfp_plan_set_symbol_upwind(s->plan, lam, mu));
   } else {
     CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
   }

@@ -348,15 +348,21 @@ PetscErrorCode cfp_pc::own_symbol_apply(Mat FFT_MAT, Vec X, Vec b) {
 // The diffusion boundary's build-specific pieces (pcshell_common.h).  The symbol goes on the
 // complex plan (grids the real plan lacks, the explicit-Diag path) and on the real plan; the
 // caller (ensure_advdiff_symbol) then records ad / ad_version, which rplan_current reads.
-PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* base, const double lam[6], const double mu[6]) {
+PetscErrorCode cfp_pc::pc_set_advdiff_symbol(ShellBase* base, const double lam[6], const double mu[6], bool upwind) {
   RShell* s = static_cast<RShell*>(base);
   if (s->slab.plan) {  // several ranks: the complex slab plan on the promoted slab, as the transport apply
-    CFPCALL(cfp_dist_plan_set_symbol_advdiff(s->slab.plan, lam, mu));
+    if (upwind) CFPCALL(cfp_dist_plan_set_symbol_upwind(s->slab.plan, lam, mu));
+    else CFPCALL(cfp_dist_plan_set_symbol_advdiff(s->slab.plan, lam, mu));
     ++s->dist_version;
     return PETSC_SUCCESS;
   }
-  CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
   const double l3[3] = {lam[0], lam[2], lam[4]}, m3[3] = {mu[0], mu[2], mu[4]};
+  if (upwind) {
+    CFPCALL(cfp_plan_set_symbol_upwind(s->plan, lam, mu));
+    if (s->rplan) CFPCALL(cfp_rplan_set_symbol_upwind(s->rplan, l3, m3));
+    return PETSC_SUCCESS;
+  }
+  CFPCALL(cfp_plan_set_symbol_advdiff(s->plan, lam, mu));
   if (s->rplan) CFPCALL(cfp_rplan_set_symbol_advdiff(s->rplan, l3, m3));
   return PETSC_SUCCESS;
 }

@@ -220,14 +220,15 @@ extern "C" PetscErrorCode TransportEquationGMRES(const cfp_transport_config* cfg
     ctx.n_x = nx;
     ctx.n_y = ny;
     ctx.n_z = nz;
-    if (cfg->lambda_mode == CFP_LAMBDA_MATCHED) {
+    const bool up = cfg->lambda_mode == CFP_LAMBDA_UPWIND;
+    if (cfg->lambda_mode == CFP_LAMBDA_MATCHED || up) {
       ctx.lambda_x = cfg->a[0] * dt / h[0];
       ctx.lambda_y = cfg->a[1] * dt / h[1];
       ctx.lambda_z = cfg->a[2] * dt / h[2];
     }
     PetscCall(PCSetType(pc, PCSHELL));
     PetscCall(PCShellSetContext(pc, &ctx));
-    PetscCall(PCShellSetSetUp(pc, setupFFTPrec3D));
+    PetscCall(PCShellSetSetUp(pc, up ? setupFFTPrec3DUpwind : setupFFTPrec3D));
     PetscCall(PCShellSetApply(pc, applyFFT3DPrecTransport));
     if (cfg->fuse) PetscCall(PCShellSetApplyBA(pc, applyFFT3DPrecTransportBA));
     PetscCall(PCShellSetDestroy(pc, destroyFFTPrec3D));

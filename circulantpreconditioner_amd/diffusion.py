@@ -19,10 +19,10 @@ from ._lib_ext import AdvDiffConfig, AdvDiffResult, PetscScalar, StructuredDiffu
 from .petsc import PETSC_COMM_SELF, Mat, PetscCall, Vec
 
 BC_WALL, BC_PERIODIC = 0, 1
-PC_NONE, PC_FFT = 0, 1
+PC_NONE, PC_FFT, PC_FFT_UPWIND = 0, 1, 2
 
 _BC = {"wall": BC_WALL, "periodic": BC_PERIODIC}
-_PC = {"none": PC_NONE, "fft": PC_FFT}
+_PC = {"none": PC_NONE, "fft": PC_FFT, "fft_upwind": PC_FFT_UPWIND}
 
 
 def _d3(v) -> ctypes.Array:
@@ -77,7 +77,7 @@ def operator(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[flo
 
 def config(n: int | Sequence[int] = 32, real: bool = False, **kw) -> AdvDiffConfig:
     """cfp_advdiff_config_default ([-0.5, 0.5]^3, a = (1, 0, 0), nu = 0.01, dt = 0.01, one step,
-    precision 1e-8, the FFT PCSHELL, walls) with keyword overrides: pc='none'|'fft',
+    precision 1e-8, the FFT PCSHELL, walls) with keyword overrides: pc='none'|'fft'|'fft_upwind',
     bc='wall'|'periodic', steps=ntmax, device=True/False, plus any AdvDiffConfig field."""
     cfg = AdvDiffConfig()
     dims = (int(n),) * 3 if np.isscalar(n) else tuple(int(v) for v in n)
@@ -144,16 +144,17 @@ def context(ndim: int, dt: float, dims: Sequence[int], a: Sequence[float], nu: f
     return ctx
 
 
-def pc_shell(ctx):
+def pc_shell(ctx, upwind: bool = False):
     """A PC of type PCSHELL with the diffusion callbacks registered on ctx (setupFFTPrec3DDiffusion,
     applyFFT3DPrecDiffusion, destroyFFTPrec3DDiffusion) and set up.  On PETSC_COMM_WORLD of several
-    ranks the FFT matrix is this rank's z slab and ctx.Diag its z-planes of the symbol."""
+    ranks the FFT matrix is this rank's z slab and ctx.Diag its z-planes of the symbol.
+    upwind=True: setupFFTPrec3DDiffusionUpwind, the operator's symbol for a velocity of either sign."""
     from .petsc import PC, _fn
     pc = PC()
     PetscCall(lib().PCSetType(pc.h, b"shell"))
     pc.ctx = ctx
     PetscCall(lib().PCShellSetContext(pc.h, ctypes.addressof(ctx)))
-    PetscCall(lib().PCShellSetSetUp(pc.h, _fn("setupFFTPrec3DDiffusion")))
+    PetscCall(lib().PCShellSetSetUp(pc.h, _fn("setupFFTPrec3DDiffusionUpwind" if upwind else "setupFFTPrec3DDiffusion")))
     PetscCall(lib().PCShellSetApply(pc.h, _fn("applyFFT3DPrecDiffusion")))
     PetscCall(lib().PCShellSetDestroy(pc.h, _fn("destroyFFTPrec3DDiffusion")))
     return pc.setup()

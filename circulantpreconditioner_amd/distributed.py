@@ -184,6 +184,12 @@ class SlabPlan:
         check(lib().cfp_dist_plan_set_symbol_advdiff(self._h, _lam6(lam), _lam6(mu)))
         return self
 
+    def set_upwind_symbol(self, lam, mu=(0, 0, 0)) -> "SlabPlan":
+        """CirculantPlan.set_upwind_symbol: the advection-diffusion symbol, upwind for either sign
+        of lambda_d."""
+        check(lib().cfp_dist_plan_set_symbol_upwind(self._h, _lam6(lam), _lam6(mu)))
+        return self
+
     def set_mid_kernel(self, mid: str | int) -> "SlabPlan":
         """Middle kernel of the 256^3 3-sweep schedule: 'auto' (the measured default), 'fft', or
         'rec' (the two-sided z recurrence wherever the symbol admits it)."""
@@ -377,6 +383,11 @@ class SlabGroup:
     def set_advdiff_symbol(self, lam, mu) -> "SlabGroup":
         """As SlabPlan.set_advdiff_symbol, on every slab."""
         check(lib().cfp_group_set_symbol_advdiff(self._h, _lam6(lam), _lam6(mu)))
+        return self
+
+    def set_upwind_symbol(self, lam, mu=(0, 0, 0)) -> "SlabGroup":
+        """As SlabPlan.set_upwind_symbol, on every slab."""
+        check(lib().cfp_group_set_symbol_upwind(self._h, _lam6(lam), _lam6(mu)))
         return self
 
     def set_mid_kernel(self, mid: str | int) -> "SlabGroup":

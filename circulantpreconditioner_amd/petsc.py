@@ -449,16 +449,17 @@ class PC:
         self.ctx = None
 
     @classmethod
-    def shell(cls, ctx: FFTPrecTransportContext) -> "PC":
+    def shell(cls, ctx: FFTPrecTransportContext, upwind: bool = False) -> "PC":
         """PCSetType(pc, PCSHELL); PCShellSetContext; PCShellSetSetUp/Apply/Destroy with the
-        reference's callbacks (the registration the reference never does, ToDo.md:1)."""
-        return cls().set_shell(ctx)
+        reference's callbacks (the registration the reference never does, ToDo.md:1).
+        upwind=True: setupFFTPrec3DUpwind, the upwind symbol for lambda_d of either sign."""
+        return cls().set_shell(ctx, upwind)
 
-    def set_shell(self, ctx: FFTPrecTransportContext) -> "PC":
+    def set_shell(self, ctx: FFTPrecTransportContext, upwind: bool = False) -> "PC":
         PetscCall(lib().PCSetType(self.h, b"shell"))
         self.ctx = ctx
         PetscCall(lib().PCShellSetContext(self.h, ctypes.addressof(ctx)))
-        PetscCall(lib().PCShellSetSetUp(self.h, _fn("setupFFTPrec3D")))
+        PetscCall(lib().PCShellSetSetUp(self.h, _fn("setupFFTPrec3DUpwind" if upwind else "setupFFTPrec3D")))
         PetscCall(lib().PCShellSetApply(self.h, _fn("applyFFT3DPrecTransport")))
         PetscCall(lib().PCShellSetDestroy(self.h, _fn("destroyFFTPrec3D")))
         return self

@@ -75,6 +75,7 @@ def _declare(L) -> None:
         "getFFTPrec3DDiffusionContext": ([i64, d, i64, i64, i64, d, d, d, d, P(d), P(d),
                                           P(FFTPrecDiffusionContext)], c_int),
         "setupFFTPrec3DDiffusion": ([vp], c_int),
+        "setupFFTPrec3DDiffusionUpwind": ([vp], c_int),
         "applyFFT3DPrecDiffusion": ([vp, vp, vp], c_int),
         "destroyFFTPrec3DDiffusion": ([vp], c_int),
         "PetscFft3DDiffusionSolver": ([StructuredDiffusionContext, vp, vp], c_int),
@@ -150,6 +151,7 @@ def _declare(L) -> None:
         "build_diag_mat_vec_3D": ([vp, vp, vp, vp, i64, i64, i64, d, d, d], c_int),
         "PetscFft3DTransportSolver": ([StructuredTransportContext, vp, vp], c_int),
         "setupFFTPrec3D": ([vp], c_int),
+        "setupFFTPrec3DUpwind": ([vp], c_int),
         "destroyFFTPrec3D": ([vp], c_int),
         "applyFFT3DPrecTransport": ([vp, vp, vp], c_int),
         "applyFFT3DPrecTransportBA": ([vp, c_int, vp, vp, vp], c_int),
@@ -371,13 +373,16 @@ def mat_destroy(M) -> None:
         PetscCall(lib().MatDestroy(ctypes.byref(M)))
 
 
-def pc_shell(ctx) -> ctypes.c_void_p:
+def pc_shell(ctx, upwind: bool = False) -> ctypes.c_void_p:
     """PCSHELL registered as ToDo.md:1 intends: context + setup / apply / destroy callbacks.  An
     FFTPrecTransportContext takes the transport trio, an FFTPrecDiffusionContext the diffusion one
-    (include/diffusion_equation.h)."""
+    (include/diffusion_equation.h).  upwind=True: the setup with the upwind symbol, for numbers of
+    either sign (setupFFTPrec3DUpwind / setupFFTPrec3DDiffusionUpwind)."""
     trio = (("setupFFTPrec3DDiffusion", "applyFFT3DPrecDiffusion", "destroyFFTPrec3DDiffusion")
             if isinstance(ctx, FFTPrecDiffusionContext)
             else ("setupFFTPrec3D", "applyFFT3DPrecTransport", "destroyFFTPrec3D"))
+    if upwind:
+        trio = (trio[0] + "Upwind",) + trio[1:]
     pc = ctypes.c_void_p()
     L = lib()
     PetscCall(L.PCCreate(PETSC_COMM_WORLD, ctypes.byref(pc)))

@@ -121,6 +121,13 @@ class CirculantPlan:
         check(lib().cfp_plan_set_symbol_advdiff(self._h, _lam6(lam), _lam6(mu)))
         return self
 
+    def set_upwind_symbol(self, lam: Sequence, mu: Sequence = (0, 0, 0)) -> "CirculantPlan":
+        """The advection-diffusion symbol, upwind for either sign of the velocity: an axis with
+        Re lambda_d < 0 contributes (-lambda_d) (1 - conj(w_d)) (a cell coupled to index + 1) instead
+        of lambda_d (1 - w_d).  With no negative axis it is set_advdiff_symbol(lam, mu)."""
+        check(lib().cfp_plan_set_symbol_upwind(self._h, _lam6(lam), _lam6(mu)))
+        return self
+
     def set_separable_symbol(self, cx_hat, cy_hat, cz_hat, lam: Sequence) -> "CirculantPlan":
         """Diag = 1 + lx*tile(cx_hat) + ly*repeat(tile(cy_hat)) + lz*repeat(cz_hat)."""
         arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.complex128).reshape(-1)) for a in (cx_hat, cy_hat, cz_hat)]
@@ -283,10 +290,12 @@ class CirculantPlan:
     def mid_kernel(self) -> str:
         """The middle kernel the next apply launches: 'zrec' (z by recurrence: 256^3, default
         shape, a transport symbol with z ratio <= 1 - 2^-13), 'zrec2' (the two-sided recurrence:
-        an advection-diffusion symbol with mu_z != 0 and both z ratios <= 1 - 2^-7) or 'fft'."""
+        an advection-diffusion symbol with mu_z != 0 and both z ratios <= 1 - 2^-7), 'zrecb' (the
+        backward recurrence: set_upwind_symbol with lambda_z < 0, mu_z = 0 and z ratio <= 1 - 2^-13)
+        or 'fft'."""
         k = ctypes.c_int()
         check(lib().cfp_plan_mid_kernel(self._h, ctypes.byref(k)))
-        return {1: "zrec", 2: "zrec2"}.get(k.value, "fft")
+        return {1: "zrec", 2: "zrec2", 3: "zrecb"}.get(k.value, "fft")
 
     def time_passes(self, b: torch.Tensor, x: torch.Tensor, iters: int = 20, stream=None) -> list:
         """Mean device time (ms) of each launch of one apply, HIP events on `stream`."""
@@ -349,6 +358,15 @@ def advdiff_symbol_1d(n: int, lam: complex, mu: complex) -> np.ndarray:
     check(lib().cfp_advdiff_symbol_1d(int(n), (ctypes.c_double * 2)(l.real, l.imag),
                                       (ctypes.c_double * 2)(m.real, m.imag), out.ctypes.data))
     return out
+
+
+def upwind_to_advdiff(lam: Sequence, mu: Sequence = (0, 0, 0)) -> tuple:
+    """(lam, mu') with which the advection-diffusion symbol is the upwind one: mu'_d = mu_d -
+    lambda_d on the axes with Re lambda_d < 0 (cfp_upwind_to_advdiff); two complex 3-vectors."""
+    lo, mo = (ctypes.c_double * 6)(), (ctypes.c_double * 6)()
+    check(lib().cfp_upwind_to_advdiff(_lam6(lam), _lam6(mu), lo, mo))
+    return (np.array([complex(lo[2 * a], lo[2 * a + 1]) for a in range(3)]),
+            np.array([complex(mo[2 * a], mo[2 * a + 1]) for a in range(3)]))
 
 
 def advdiff_z_ratio(nx: int, ny: int, lam: Sequence, mu: Sequence) -> tuple:
@@ -425,6 +443,11 @@ class RealPlan:
         """Diag = 1 + sum_d [lambda_d (1 - w_d) + mu_d (2 - w_d - conj(w_d))] for real lambda_d =
         a_d dt / h_d and mu_d = nu dt / h_d^2 (CirculantPlan.set_advdiff_symbol's closed form)."""
         check(lib().cfp_rplan_set_symbol_advdiff(self._h, self._real3(lam, "lambda"), self._real3(mu, "mu")))
+        return self
+
+    def set_upwind_symbol(self, lam: Sequence, mu: Sequence = (0, 0, 0)) -> "RealPlan":
+        """CirculantPlan.set_upwind_symbol for real lambda_d of either sign and real mu_d."""
+        check(lib().cfp_rplan_set_symbol_upwind(self._h, self._real3(lam, "lambda"), self._real3(mu, "mu")))
         return self
 
     MID_KERNELS = {"auto": 0, "fft": 1, "rec": 2}

@@ -18,11 +18,11 @@ from .petsc import PetscCall
 
 UPWIND_REFERENCE, UPWIND_FIXED = 0, 1
 PC_NONE, PC_FFT = 0, 1
-LAMBDA_REFERENCE, LAMBDA_MATCHED = 0, 1
+LAMBDA_REFERENCE, LAMBDA_MATCHED, LAMBDA_UPWIND = 0, 1, 2
 
 _SIGN = {"reference": UPWIND_REFERENCE, "faithful": UPWIND_REFERENCE, "fixed": UPWIND_FIXED}
 _PC = {"none": PC_NONE, "fft": PC_FFT}
-_LAM = {"reference": LAMBDA_REFERENCE, "matched": LAMBDA_MATCHED}
+_LAM = {"reference": LAMBDA_REFERENCE, "matched": LAMBDA_MATCHED, "upwind": LAMBDA_UPWIND}
 
 
 def _d3(v) -> ctypes.Array:
@@ -54,7 +54,8 @@ def min_ratio_vol_surf(dim: int, h: Sequence[float]) -> float:
 def config(n: int | Sequence[int] = 32, **kw) -> TransportConfig:
     """The reference main's defaults (cube [-0.5,0.5]^3, a=(1,0,0), cfl=1e3/3, tmax=0.05,
     precision 1e-5, 1000 KSP iterations) with keyword overrides:
-    pc='none'|'fft', sign='reference'|'fixed', lam='reference'|'matched', steps=ntmax,
+    pc='none'|'fft', sign='reference'|'fixed', lam (or lambda_mode)='reference'|'matched'|'upwind'
+    (the matched numbers with the upwind setup, for a velocity of either sign), steps=ntmax,
     device=True/False, plus any TransportConfig field."""
     cfg = TransportConfig()
     dims = (int(n),) * 3 if np.isscalar(n) else tuple(int(v) for v in n)
@@ -65,7 +66,7 @@ def config(n: int | Sequence[int] = 32, **kw) -> TransportConfig:
             cfg.pc = _PC[v] if isinstance(v, str) else int(v)
         elif k == "sign":
             cfg.sign_mode = _SIGN[v] if isinstance(v, str) else int(v)
-        elif k == "lam":
+        elif k in ("lam", "lambda_mode"):
             cfg.lambda_mode = _LAM[v] if isinstance(v, str) else int(v)
         elif k == "steps":
             cfg.ntmax = int(v)

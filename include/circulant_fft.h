@@ -77,6 +77,20 @@ int cfp_plan_set_symbol_transport(cfp_plan_t plan, const double lam[6]);
  * above, axes with n_d == 1 contribute 0, and mu = 0 is the transport symbol, bit for bit.  It
  * fills the separable tables, so every schedule serves it. */
 int cfp_plan_set_symbol_advdiff(cfp_plan_t plan, const double lam[6], const double mu[6]);
+/* The same symbol, upwind for either sign of the velocity:
+ *   Diag[k] = 1 + sum_d [ up_d + mu_d (2 - w_d - conj(w_d)) ],
+ *   up_d = lambda_d (1 - w_d) for Re lambda_d >= 0, (-lambda_d) (1 - conj(w_d)) otherwise
+ * (a cell coupled to index - 1 or to index + 1: the operators of cfp_transport_csr with
+ * CFP_UPWIND_FIXED and of cfp_advdiff_csr).  It fills the separable tables through
+ * cfp_plan_set_symbol_advdiff with the numbers of cfp_upwind_to_advdiff, so every schedule serves
+ * it; with no negative axis it is that setter, bit for bit and in its routing.  At 256^3 a
+ * symbol with Re lambda_z < 0 and mu_z == 0 may take the backward z recurrence
+ * (cfp_plan_mid_kernel). */
+int cfp_plan_set_symbol_upwind(cfp_plan_t plan, const double lam[6], const double mu[6]);
+/* host (no GPU needed): the pair with which the advection-diffusion symbol is the upwind one,
+ *   |lam| (1 - conj w) + mu (2 - w - conj w) = lam (1 - w) + (mu - lam) (2 - w - conj w)  for lam < 0:
+ * per axis with Re lambda_d < 0 lam_out = lambda_d and mu_out = mu_d - lambda_d, otherwise a copy. */
+int cfp_upwind_to_advdiff(const double lam[6], const double mu[6], double lam_out[6], double mu_out[6]);
 /* Separable symbol from caller-given 1-D eigenvalue vectors (host arrays of n_x, n_y, n_z
  * complex values, e.g. the 1-D DFTs of arbitrary circulant columns):
  * Diag = 1 + lx*tile(cx_hat) + ly*repeat(tile(cy_hat)) + lz*repeat(cz_hat)   (:136-164). */
@@ -194,10 +208,15 @@ int cfp_plan_set_three_pass_shape(cfp_plan_t plan, int n1, int mid);
  * cfp_plan_set_symbol_transport (or cfp_plan_set_symbol_advdiff with mu_z == 0) whose z ratio
  * (cfp_transport_z_ratio) is at most 1 - 2^-13; the two-sided one for a symbol set by
  * cfp_plan_set_symbol_advdiff with mu_z != 0 whose two z ratios (cfp_advdiff_z_ratio) are both
- * at most 1 - 2^-7; CFP_TP_MID_SWAP64_PF is the FFT kernel always. */
+ * at most 1 - 2^-7; CFP_TP_MID_SWAP64_PF is the FFT kernel always.  CFP_MID_KERNEL_ZREC_BACK is
+ * the backward recurrence u_z = a u_{z+1} + w_z (the forward kernel on the planes in reverse
+ * order): only for a symbol set by cfp_plan_set_symbol_upwind with Re lambda_z < 0 and mu_z == 0
+ * whose ratio max |b| of cfp_advdiff_z_ratio on the mapped numbers is at most 1 - 2^-13; over
+ * that cap it is the FFT kernel, and with mu_z != 0 the rule of the mapped advdiff symbol. */
 #define CFP_MID_KERNEL_FFT 0
 #define CFP_MID_KERNEL_ZREC 1
 #define CFP_MID_KERNEL_ZREC2 2
+#define CFP_MID_KERNEL_ZREC_BACK 3
 int cfp_plan_mid_kernel(cfp_plan_t plan, int *kind);
 
 /* Introspection: number of kernel launches of one apply, and per-launch timing.

@@ -147,6 +147,10 @@ int cfp_dist_plan_set_symbol_transport(cfp_dist_plan_t plan, const double lam[6]
  * closed form that was set last: a new schedule or piece count refills its tables, and
  * cfp_dist_plan_clear_diag / cfp_dist_plan_use_diag(plan, 0) return to it. */
 int cfp_dist_plan_set_symbol_advdiff(cfp_dist_plan_t plan, const double lam[6], const double mu[6]);
+/* The upwind symbol of cfp_plan_set_symbol_upwind (circulant_fft.h): cfp_dist_plan_set_symbol_advdiff
+ * with the numbers of cfp_upwind_to_advdiff, which the plan remembers and whose routing it keeps
+ * (the slab plan has no backward-recurrence kernel). */
+int cfp_dist_plan_set_symbol_upwind(cfp_dist_plan_t plan, const double lam[6], const double mu[6]);
 /* Middle kernel of the 3-sweep schedule at 256^3.  With the advection-diffusion symbol, mu_z != 0
  * and both z ratios of the whole grid (cfp_advdiff_z_ratio) <= 1 - 2^-7, the rank's z-pencil block
  * may take the two-sided z recurrence of the one-GPU plan (CFP_MID_KERNEL_ZREC2) instead of the
@@ -205,6 +209,7 @@ int cfp_group_create(cfp_group_t *group, int64_t nx, int64_t ny, int64_t nz, int
 int cfp_group_destroy(cfp_group_t group);
 int cfp_group_set_symbol_transport(cfp_group_t group, const double lam[6]);
 int cfp_group_set_symbol_advdiff(cfp_group_t group, const double lam[6], const double mu[6]); /* as cfp_dist_plan_* */
+int cfp_group_set_symbol_upwind(cfp_group_t group, const double lam[6], const double mu[6]);  /* as cfp_dist_plan_* */
 int cfp_group_set_mid_kernel(cfp_group_t group, int mode);
 int cfp_group_mid_kernel(cfp_group_t group, int *kind);
 /* b_devs[r], x_devs[r]: slab r on devices[r]; synchronous */

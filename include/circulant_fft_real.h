@@ -41,6 +41,10 @@ int cfp_rplan_set_symbol_transport(cfp_rplan_t plan, const double lam[3]);
  * w_d = e^{-i theta_d}, for real lambda_d = a_d dt / h_d and mu_d = nu dt / h_d^2: the closed form
  * of cfp_plan_set_symbol_advdiff (circulant_fft.h); mu = 0 gives the transport setter's tables */
 int cfp_rplan_set_symbol_advdiff(cfp_rplan_t plan, const double lam[3], const double mu[3]);
+/* the same symbol, upwind for either sign of lambda_d (cfp_plan_set_symbol_upwind, circulant_fft.h):
+ * cfp_rplan_set_symbol_advdiff with the numbers of cfp_upwind_to_advdiff (lambda_d < 0: mu_d -
+ * lambda_d), whose routing it keeps; this plan has no backward-recurrence kernel */
+int cfp_rplan_set_symbol_upwind(cfp_rplan_t plan, const double lam[3], const double mu[3]);
 /* x = C^{-1} b for real b (nx*ny*nz doubles on the device); x may alias b */
 int cfp_rplan_apply(cfp_rplan_t plan, const double *b, double *x, void *stream);
 /* schedule: CFP_RSCHEDULE_AUTO (3 sweeps at 128^3 and 256^3, else r2c + 3 half-spectrum passes + c2r),

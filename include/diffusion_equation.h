@@ -15,7 +15,10 @@
  *   Diag[k] = 1 + sum_d [ lambda_d (1 - w_d) + mu_d (2 - w_d - conj(w_d)) ],  w_d = e^{-2 pi i k_d/n_d},
  *   lambda_d = a_d dt / h_d,  mu_d = nu dt / h_d^2   (cfp_plan_set_symbol_advdiff),
  * exactly for a_d >= 0 (the advection part couples a cell to its neighbour at index - 1, as the
- * transport symbol does).  Registration by the caller:
+ * transport symbol does).  For a velocity with a negative component the operator couples that axis
+ * to index + 1 and its symbol is the upwind one (cfp_plan_set_symbol_upwind, circulant_fft.h):
+ * setupFFTPrec3DDiffusionUpwind below sets it, for either sign of every a_d.  Registration by the
+ * caller:
  *   PCSetType(pc, PCSHELL); PCShellSetContext(pc, &ctx);
  *   PCShellSetSetUp(pc, setupFFTPrec3DDiffusion); PCShellSetApply(pc, applyFFT3DPrecDiffusion);
  *   PCShellSetDestroy(pc, destroyFFTPrec3DDiffusion);
@@ -92,6 +95,9 @@ PetscErrorCode getFFTPrec3DDiffusionContext(PetscInt ndim, PetscScalar dt, Petsc
  * from the plan's closed-form symbol); the apply divides by the plan's own symbol in registers
  * while Diag is untouched, as applyFFT3DPrecTransport does. */
 PetscErrorCode setupFFTPrec3DDiffusion(PC pc);
+/* setupFFTPrec3DDiffusion with the upwind symbol (cfp_plan_set_symbol_upwind): lambda_d of either
+ * sign.  Diag is that symbol; apply and destroy are the callbacks below.  One rank or several. */
+PetscErrorCode setupFFTPrec3DDiffusionUpwind(PC pc);
 PetscErrorCode applyFFT3DPrecDiffusion(PC pc, Vec b, Vec x);
 PetscErrorCode destroyFFTPrec3DDiffusion(PC pc);
 
@@ -119,7 +125,9 @@ PetscErrorCode computeAdvectionDiffusionMatrixCartesianAIJ(MPI_Comm comm, PetscI
                                                            PetscReal nu, PetscInt bc, Mat *A);
 
 /* ---- the implicit time loop with GMRES */
-enum { CFP_ADVDIFF_PC_NONE = 0, CFP_ADVDIFF_PC_FFT = 1 };
+/* FFT_UPWIND: the PCSHELL with setupFFTPrec3DDiffusionUpwind (the operator's symbol for a velocity
+ * of either sign); FFT keeps setupFFTPrec3DDiffusion */
+enum { CFP_ADVDIFF_PC_NONE = 0, CFP_ADVDIFF_PC_FFT = 1, CFP_ADVDIFF_PC_FFT_UPWIND = 2 };
 
 typedef struct {
   int64_t nx, ny, nz;

@@ -74,6 +74,12 @@ struct StructuredTransportContext {
 PetscErrorCode applyFFT3DPrecTransport(PC pc, Vec b, Vec x);
 PetscErrorCode setupFFTPrec3D(PC pc);
 PetscErrorCode destroyFFTPrec3D(PC pc);
+/* Not in the reference: setupFFTPrec3D with the upwind symbol (cfp_plan_set_symbol_upwind,
+ * circulant_fft.h), for lambda_d of either sign -- an axis with Re lambda_d < 0 couples a cell to
+ * index + 1, as the CFP_UPWIND_FIXED operator does (the literal lambda (1 - w) there is the
+ * downwind scheme's symbol).  Diag is materialised from it; apply, applyBA and destroy are the
+ * callbacks above.  One rank or several, both scalar builds. */
+PetscErrorCode setupFFTPrec3DUpwind(PC pc);
 /* Not in the reference (an addition for its GMRES caller, tests/TransportEquation_SphericalExplosion_
  * impl_mpi.cxx:120-136): the PCShellSetApplyBA callback, y = B A x (left) / A B x (right) with the
  * PC's operator.  On one rank with the stand-in AIJ it forms A x inside the apply's first sweep

@@ -61,7 +61,10 @@ PetscErrorCode computeDivergenceMatrixCartesianAIJ(MPI_Comm comm, PetscInt nx, P
 enum { CFP_TRANSPORT_PC_NONE = 0, CFP_TRANSPORT_PC_FFT = 1 };
 /* lambda of the FFT preconditioner: REFERENCE = getFFTPrec3DContext's a dt (max-min)/n
  * (src/PCSHELLFft_3D.cxx:146-148); MATCHED = a dt / h, the symbol of the operator. */
-enum { CFP_LAMBDA_REFERENCE = 0, CFP_LAMBDA_MATCHED = 1 };
+/* UPWIND = the MATCHED numbers with setupFFTPrec3DUpwind (pcshell_fft3d.h): the symbol of the
+ * CFP_UPWIND_FIXED operator for a velocity of either sign (TransportEquationGMRES; the
+ * unstructured-mesh driver takes REFERENCE and MATCHED) */
+enum { CFP_LAMBDA_REFERENCE = 0, CFP_LAMBDA_MATCHED = 1, CFP_LAMBDA_UPWIND = 2 };
 
 typedef struct {
   int64_t nx, ny, nz;

@@ -7,6 +7,8 @@
                                                              # the advection-diffusion symbol: zrec2 against fft
   python tools/ab_sched.py 256 real:three,fft real:three,rec --lam 0 0 0 --mu 0.3 0.3 1000
                                                              # the same on the real plan's half spectrum
+  python tools/ab_sched.py 256 three:0,default three:0,swap64pf --upwind --lam 0.6 0.15 -0.6
+                                                             # the upwind symbol: zrecb against fft
 
 Every variant applies the same b (SplitMix64 U[-1,1) complex, the bench's transport symbol) in
 place on the current stream, timed with HIP events over `--iters` back-to-back applies; the
@@ -34,6 +36,8 @@ def main() -> int:
     ap.add_argument("--mu", type=float, nargs=3, default=None,
                     help="diffusion numbers: every plan takes set_advdiff_symbol(lam, mu); a real variant's "
                          "suffix picks its middle kernel (real:three,rec / real:three,fft / real:three,auto)")
+    ap.add_argument("--upwind", action="store_true",
+                    help="every plan takes set_upwind_symbol(lam, mu or 0): lam of either sign")
     ap.add_argument("--lib", default=None, help="another build of libcirculant_fft.so (A/B of two builds)")
     args = ap.parse_args()
     if args.lib:
@@ -49,7 +53,9 @@ def main() -> int:
     for v in args.variants:
         if v.startswith("real:"):
             p = cp.RealPlan(n)
-            if args.mu is not None:
+            if args.upwind:
+                p.set_upwind_symbol(tuple(args.lam), tuple(args.mu or (0, 0, 0)))
+            elif args.mu is not None:
                 p.set_advdiff_symbol(tuple(args.lam), tuple(args.mu))
             else:
                 p.set_transport_symbol(tuple(args.lam))
@@ -60,7 +66,9 @@ def main() -> int:
             plans.append(p)
             continue
         p = cp.CirculantPlan(n)
-        if args.mu is not None:
+        if args.upwind:
+            p.set_upwind_symbol(tuple(args.lam), tuple(args.mu or (0, 0, 0)))
+        elif args.mu is not None:
             p.set_advdiff_symbol(tuple(args.lam), tuple(args.mu))
         else:
             p.set_transport_symbol(tuple(args.lam))
