@@ -161,6 +161,7 @@ def declare(L) -> None:
         "cfp_upwind_to_advdiff": ([dp, dp, dp, dp], c_int),
         "cfp_advdiff_symbol_1d": ([i64, P(ctypes.c_double), P(ctypes.c_double), dp], c_int),
         "cfp_advdiff_z_ratio": ([i64, i64, dp, dp, P(ctypes.c_double)], c_int),
+        "cfp_symbol_z_route": ([i64, i64, i64, dp, dp, c_int, P(c_int), P(ctypes.c_double)], c_int),
         # slab-distributed plan over RCCL + single-process group
         "cfp_dist_get_unique_id": ([ctypes.c_char_p], c_int),
         "cfp_dist_unique_id_bytes": ([], c_int),

@@ -291,31 +291,14 @@ hipError_t launch_repack(const cd* in, cd* out, const SlabLayout& L, i64 planes,
   return hipGetLastError();
 }
 
-enum { SYM_TRANSPORT = 1, SYM_ADVDIFF = 2 };
-
 // the 256^3 slab recurrence: P | 32, P <= 16 (three_pass_slab_supported at 256^3)
 bool slab_rec2_ranks(int P) { return P >= 1 && P <= 16 && 32 % P == 0; }
 
-// Rank r's column table of k_tp_mid_rec2 on its z-pencil block [256 z][256 / P][256 x]
-// (advdiff_z_table's layout [unit][a, r = 256 / beta, b][lane]): 32 (32 / P) units, unit u lane
-// x + 8 y2 holding kx = 8 (u % 32) + x, ky = k1_off + u / 32 + 32 brev3(y2), k1_off = r 32 / P
+// Rank r's column table of k_tp_mid_rec2 on its z-pencil block [256 z][256 / P][256 x]:
+// advdiff_z_table's 32 / P rows of units from k1_off = r 32 / P on
 std::vector<cd> slab_z_table(int P, int r, const std::vector<cd>& sx, const std::vector<cd>& sy,
                              std::complex<double> lz, std::complex<double> mz) {
-  const std::complex<double> p = lz + mz, q = mz;
-  const int nk1 = 32 / P, k1_off = r * nk1, units = 32 * nk1;
-  std::vector<cd> t((size_t)units * 3 * 64);
-  for (int u = 0; u < units; ++u)
-    for (int lane = 0; lane < 64; ++lane) {
-      const int x = lane & 7, y2 = lane >> 3;
-      const int k2 = ((y2 & 1) << 2) | (y2 & 2) | (y2 >> 2);
-      const std::complex<double> be =
-          advdiff_z_beta(sx[(size_t)(8 * (u % 32) + x)], sy[(size_t)(k1_off + u / 32 + 32 * k2)], p, q);
-      const std::complex<double> a = p / be, b = q / be, rr = 256.0 / be;
-      t[(size_t)((3 * u) * 64 + lane)] = make_cd(a.real(), a.imag());
-      t[(size_t)((3 * u + 1) * 64 + lane)] = make_cd(rr.real(), rr.imag());
-      t[(size_t)((3 * u + 2) * 64 + lane)] = make_cd(b.real(), b.imag());
-    }
-  return t;
+  return advdiff_z_table(sx, sy, lz, mz, 32, 32 / P, r * (32 / P));
 }
 
 // CFP_SLAB_MID_AUTO: the rank counts at which the recurrence replaces the FFT middle kernel, i.e.
@@ -343,8 +326,7 @@ struct SlabRank {
   bool diag = false;      // explicit Diag set (cfp_dist_plan_set_diag)
   int schedule = CFP_SCHEDULE_AUTO;
   int pieces_req = 0;     // 0 = AUTO
-  // the closed form that is set (sym): its kind and numbers, so that set_steps refills its tables
-  int sym_kind = SYM_TRANSPORT;
+  // the closed form that is set (sym): its numbers (mu = 0: transport), so that set_steps refills its tables
   double lam_[6] = {0, 0, 0, 0, 0, 0};
   double mu_[6] = {0, 0, 0, 0, 0, 0};
   // the advection-diffusion symbol on the 256^3 3-sweep schedule with mu_z != 0 and both z ratios
@@ -395,11 +377,13 @@ struct SlabRank {
         }
     return sym ? refill() : CFP_SUCCESS;  // the new schedule's symbol tables
   }
-  int refill() { return sym_kind == SYM_ADVDIFF ? set_advdiff(lam_, mu_) : set_transport(lam_); }
+  int refill() { return set_advdiff(lam_, mu_); }
   // what the next apply's 3-sweep stage 1 launches: the recurrence (AUTO: slab_rec2_auto)
   bool use_rec2() const {
     return three() && zrec2_ok && mid != CFP_SLAB_MID_FFT && (mid == CFP_SLAB_MID_REC || slab_rec2_auto(L.P));
   }
+  // the one grid and schedule k_tp_mid_rec2's slab launcher is built for
+  bool rec2_grid() const { return three() && L.nx == 256; }
   void drop_zrec2() {
     zrec2_ok = false;
     if (zrec2_tab) hipFree(zrec2_tab);
@@ -417,28 +401,10 @@ struct SlabRank {
     drop_zrec2();
     colsym = colsym3 = axsym = work = work2 = diag_t = nullptr;
   }
-  // one axis' part of the transport symbol, lambda (1 - e^{-2 pi i k / n})
-  static std::vector<cd> transport_axis(i64 n, double lr, double li) {
-    const std::vector<cd> hat = host_transport_symbol(n);
-    std::vector<cd> s(hat.size());
-    for (size_t k = 0; k < hat.size(); ++k) {
-      const double cr = hat[k].x, ci = hat[k].y;
-      s[k] = make_cd(cr * lr - ci * li, cr * li + ci * lr);
-    }
-    return s;
-  }
+  // the transport symbol: the advection-diffusion one with mu = 0 (its tables byte for byte: below)
   int set_transport(const double lam[6]) {
-    const i64 n[3] = {L.nx, L.ny, L.nz};
-    std::vector<cd> s[3];
-    for (int a = 0; a < 3; ++a) s[a] = transport_axis(n[a], lam[2 * a], lam[2 * a + 1]);
-    int rc = upload_tables(s);
-    if (rc) return rc;
-    drop_zrec2();
-    std::memmove(lam_, lam, sizeof(lam_));
-    std::memset(mu_, 0, sizeof(mu_));
-    sym_kind = SYM_TRANSPORT;
-    sym = true;
-    return CFP_SUCCESS;
+    const double mu0[6] = {0, 0, 0, 0, 0, 0};
+    return set_advdiff(lam, mu0);
   }
   // The advection-diffusion symbol (cfp_plan_set_symbol_advdiff's): the same tables from
   // host_advdiff_symbol per axis.  An axis with mu = 0 takes the transport product itself, so
@@ -447,21 +413,15 @@ struct SlabRank {
     const i64 n[3] = {L.nx, L.ny, L.nz};
     std::vector<cd> s[3];
     for (int a = 0; a < 3; ++a) {
-      if (mu[2 * a] == 0.0 && mu[2 * a + 1] == 0.0) s[a] = transport_axis(n[a], lam[2 * a], lam[2 * a + 1]);
-      else s[a] = host_advdiff_symbol(n[a], {lam[2 * a], lam[2 * a + 1]}, {mu[2 * a], mu[2 * a + 1]});
+      const std::complex<double> l(lam[2 * a], lam[2 * a + 1]), m(mu[2 * a], mu[2 * a + 1]);
+      s[a] = m == 0.0 ? transport_product(host_transport_symbol(n[a]), l) : host_advdiff_symbol(n[a], l, m);
     }
     int rc = upload_tables(s);
     if (rc) return rc;
     // the 256^3 middle sweep by recurrence: decided on the whole grid's columns, so every rank
     // decides the same way; the table holds this rank's k1 rows only
     const std::complex<double> lz(lam[4], lam[5]), mz(mu[4], mu[5]);
-    bool ok = three() && L.nx == 256 && mz != 0.0;
-    if (ok) {
-      double r[2];
-      advdiff_z_ratio(s[0], s[1], lz, mz, r);
-      ok = r[0] <= kZrec2MaxRatio && r[1] <= kZrec2MaxRatio;
-    }
-    if (ok) {
+    if (rec2_grid() && decide_z_route(s[0], s[1], lz, mz, false).route == Z_REC2) {
       const std::vector<cd> t = slab_z_table(L.P, L.r, s[0], s[1], lz, mz);
       if (!zrec2_tab) HIPCHK(hipMalloc(&zrec2_tab, sizeof(cd) * t.size()));  // (hipMalloc: 256-byte aligned)
       HIPCHK(hipMemcpy(zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
@@ -471,7 +431,6 @@ struct SlabRank {
     }
     std::memmove(lam_, lam, sizeof(lam_));
     std::memmove(mu_, mu, sizeof(mu_));
-    sym_kind = SYM_ADVDIFF;
     sym = true;
     return CFP_SUCCESS;
   }
@@ -479,20 +438,13 @@ struct SlabRank {
   // (global ky = y0 + iyl); axsym over kz
   int upload_tables(const std::vector<cd> s[3]) {
     const i64 ncols = L.nx * L.nyl;  // 0 on a rank past the last y row (padded layouts)
-    std::vector<cd> col((size_t)(ncols > 0 ? ncols : 1));
-    for (i64 g = 0; g < ncols; ++g) {
-      const i64 ix = g % L.nx, ky = L.y0 + g / L.nx;
-      col[(size_t)g] = make_cd(s[0][ix].x + s[1][ky].x, s[0][ix].y + s[1][ky].y);
-    }
+    const std::vector<cd> col = column_sums(s[0], 0, L.nx, s[1], L.y0, L.nyl > 0 ? L.nyl : 0, L.nx);
     if (!colsym) HIPCHK(hipMalloc(&colsym, sizeof(cd) * (size_t)(ncols > 0 ? ncols : 1)));
     if (!axsym) HIPCHK(hipMalloc(&axsym, sizeof(cd) * (size_t)L.nz));
-    HIPCHK(hipMemcpy(colsym, col.data(), sizeof(cd) * (size_t)ncols, hipMemcpyHostToDevice));
+    if (ncols > 0) HIPCHK(hipMemcpy(colsym, col.data(), sizeof(cd) * (size_t)ncols, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(axsym, s[2].data(), sizeof(cd) * (size_t)L.nz, hipMemcpyHostToDevice));
     if (three()) {  // every rank holds the global column table: P2 indexes it with global ky
-      std::vector<cd> g((size_t)(L.nx * L.ny));
-      for (i64 ky = 0; ky < L.ny; ++ky)
-        for (i64 ix = 0; ix < L.nx; ++ix)
-          g[(size_t)(ix + L.nx * ky)] = make_cd(s[0][ix].x + s[1][ky].x, s[0][ix].y + s[1][ky].y);
+      const std::vector<cd> g = column_sums(s[0], 0, L.nx, s[1], 0, L.ny, L.nx);
       if (!colsym3) HIPCHK(hipMalloc(&colsym3, sizeof(cd) * g.size()));
       HIPCHK(hipMemcpy(colsym3, g.data(), sizeof(cd) * g.size(), hipMemcpyHostToDevice));
     }

@@ -7,6 +7,9 @@
 //   * the symbol: separable tables (colsym over the fused axis' columns, axsym over its
 //     points) generated once, or an explicit Diag vector for a general symbol.
 // An apply reads b, writes x, and needs no scratch (x is the work buffer).
+// The closed-form symbols' arithmetic and the rule that picks the 256^3 middle kernel are
+// cfp_symbol.cpp's (decide_z_route); the plan stores the decision (z_route) and plan_z_route()
+// is the one place that says what the next apply launches.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -83,100 +86,6 @@ std::vector<cd> host_twiddles(int n, int sign) {
   return t;
 }
 
-// 1 - e^{-2 pi i k / n}: the 1-D DFT of the transport column (1, -1, 0, ...)
-std::vector<cd> host_transport_symbol(i64 n) {
-  std::vector<cd> s((size_t)n, make_cd(0.0, 0.0));
-  if (n <= 1) return s;
-  for (i64 k = 0; k < n; ++k) {
-    long double a = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
-    s[k] = make_cd((double)(1.0L - cosl(a)), (double)sinl(a));
-  }
-  return s;
-}
-
-// max over (kx, ky) of |lamz / (1 + sx[kx] + sy[ky] + lamz)|, s_d = lambda_d (1 - e^{-2 pi i k / n_d}):
-// the ratio a of the z recurrence u_z = a u_{z-1} + w_z that the transport symbol's z part is
-// (cfp_three_pass.hip k_tp_mid_rec).  A zero denominator gives infinity.
-double transport_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz) {
-  double amax = 0.0;
-  const double lzn = std::abs(lz);
-  for (const cd& y : sy)
-    for (const cd& x : sx) {
-      const std::complex<double> den(x.x + y.x + 1.0 + lz.real(), x.y + y.y + lz.imag());
-      const double d = std::abs(den);
-      const double r = d > 0.0 ? lzn / d : (lzn > 0.0 ? INFINITY : 0.0);
-      if (!(r <= amax)) amax = r;
-    }
-  return amax;
-}
-// the recurrence's rounding grows like eps / (1 - |a|): this cap keeps it near 1e-12
-constexpr double kZrecMaxRatio = 1.0 - 1.0 / 8192.0;
-
-// lambda (1 - w) + mu (2 - w - conj(w)), w = e^{-2 pi i k / n}: one axis' part of the
-// advection-diffusion symbol (0 for n == 1)
-std::vector<cd> host_advdiff_symbol(i64 n, std::complex<double> lam, std::complex<double> mu) {
-  std::vector<cd> s((size_t)n, make_cd(0.0, 0.0));
-  if (n <= 1) return s;
-  const std::vector<cd> hat = host_transport_symbol(n);
-  for (i64 k = 0; k < n; ++k) {
-    // the advection part exactly as the transport setter forms it (set_separable), so that mu = 0
-    // gives its tables bit for bit; 2 - w - conj(w) = 2 Re(1 - w)
-    const double re = hat[k].x * lam.real() - hat[k].y * lam.imag();
-    const double im = hat[k].x * lam.imag() + hat[k].y * lam.real();
-    const double c2 = 2.0 * hat[k].x;
-    s[k] = make_cd(re + mu.real() * c2, im + mu.imag() * c2);
-  }
-  return s;
-}
-
-// Along z the advection-diffusion symbol of a column, d - p e^{-i theta} - q e^{i theta} with
-// p = lamz + muz, q = muz, d = 1 + sx[kx] + sy[ky] + p + q, factors as
-// beta (1 - a e^{-i theta}) (1 - b e^{i theta}), beta the root of beta^2 - d beta + p q = 0 of
-// larger modulus, a = p / beta, b = q / beta (cfp_three_pass.hip k_tp_mid_rec2).  ratios = max |a|,
-// max |b| over the columns; beta = 0 gives infinity.
-std::complex<double> advdiff_z_beta(cd x, cd y, std::complex<double> p, std::complex<double> q) {
-  const std::complex<double> d = std::complex<double>(x.x + y.x + 1.0, x.y + y.y) + p + q;
-  if (q == 0.0) return d;  // first order: the roots are d and 0 (a is the transport ratio exactly)
-  std::complex<double> sq = std::sqrt(d * d - 4.0 * p * q);
-  if (d.real() * sq.real() + d.imag() * sq.imag() < 0.0) sq = -sq;  // the root on d's side is the larger
-  return 0.5 * (d + sq);
-}
-void advdiff_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz,
-                     std::complex<double> mz, double ratios[2]) {
-  const std::complex<double> p = lz + mz, q = mz;
-  const double pn = std::abs(p), qn = std::abs(q);
-  ratios[0] = ratios[1] = 0.0;
-  for (const cd& y : sy)
-    for (const cd& x : sx) {
-      const double bn = std::abs(advdiff_z_beta(x, y, p, q));
-      const double ra = bn > 0.0 ? pn / bn : (pn > 0.0 ? INFINITY : 0.0);
-      const double rb = bn > 0.0 ? qn / bn : (qn > 0.0 ? INFINITY : 0.0);
-      if (!(ra <= ratios[0])) ratios[0] = ra;
-      if (!(rb <= ratios[1])) ratios[1] = rb;
-    }
-}
-// k_tp_mid_rec2's column table at 256^3 (cfp_three_pass.h): [unit u][a, r = 256 / beta, b][lane],
-// lane = x + 8 y2 holding column kx = 8 (u % nxt) + x, ky = u / nxt + 32 brev3(y2); nxt x tiles
-// per row: 32 on the complex grid (1024 units), 16 on the real plan's half spectrum (512 units)
-std::vector<cd> advdiff_z_table(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz,
-                                std::complex<double> mz, int nxt) {
-  const std::complex<double> p = lz + mz, q = mz;
-  const int units = 32 * nxt;
-  std::vector<cd> t((size_t)units * 3 * 64);
-  for (int u = 0; u < units; ++u)
-    for (int lane = 0; lane < 64; ++lane) {
-      const int x = lane & 7, y2 = lane >> 3;
-      const int k2 = ((y2 & 1) << 2) | (y2 & 2) | (y2 >> 2);
-      const std::complex<double> be = advdiff_z_beta(sx[(size_t)(8 * (u % nxt) + x)], sy[(size_t)(u / nxt + 32 * k2)], p, q);
-      const std::complex<double> a = p / be, b = q / be, r = 256.0 / be;
-      t[(size_t)((3 * u) * 64 + lane)] = make_cd(a.real(), a.imag());
-      t[(size_t)((3 * u + 1) * 64 + lane)] = make_cd(r.real(), r.imag());
-      t[(size_t)((3 * u + 2) * 64 + lane)] = make_cd(b.real(), b.imag());
-    }
-  return t;
-}
-// (the cap of both ratios: kZrec2MaxRatio, cfp_host.h)
-
 int ilog2_exact(i64 v) {
   if (v <= 0 || (v & (v - 1))) return -1;
   int l = 0;
@@ -244,22 +153,12 @@ struct cfp_plan_s {
   i64 chunk_planes = 0;      // > 0: chunked x/y schedule (see apply_steps)
   int schedule = CFP_SCHEDULE_AUTO;
   TPShape tp_shape;          // 3-sweep kernel shape (cfp_plan_set_three_pass_shape)
-  // the transport symbol's z ratio (cfp_plan_set_symbol_transport): zrec_ok = every column's
-  // |lamz / (1 + s_x + s_y + lamz)| <= 1 - 2^-13, so the 256^3 P2 may solve z by recurrence
-  // (k_tp_mid_rec).  Any other symbol setter clears it.
-  bool zrec_ok = false;
-  double zrec_amax = 0.0;
+  // how the 256^3 P2 may solve z for the symbol that is set (decide_z_route, cfp_symbol.h; every
+  // setter but the transport, advdiff and upwind ones leaves Z_FFT): lamz goes to k_tp_mid_rec or
+  // k_tp_mid_recb, zrec2_tab (device, advdiff_z_table; allocated on first use) to k_tp_mid_rec2
+  ZRoute z_route = Z_FFT;
   cd lamz = cfp::make_cd(0.0, 0.0);
-  // the advection-diffusion symbol's z factors (cfp_plan_set_symbol_advdiff with muz != 0):
-  // zrec2_ok = every column's |a| and |b| <= 1 - 2^-7, so the 256^3 P2 may solve z by the
-  // two-sided recurrence (k_tp_mid_rec2) from the columns' factors in zrec2_tab (device,
-  // advdiff_z_table; allocated with the first eligible symbol)
-  bool zrec2_ok = false;
   cd* zrec2_tab = nullptr;
-  // the upwind symbol with Re lamz < 0 and muz == 0 (cfp_plan_set_symbol_upwind only): zrecb_ok =
-  // every column's |q / (1 + s_x + s_y + q)| <= 1 - 2^-13, q = -lamz, so the 256^3 P2 may solve z
-  // by the backward recurrence (k_tp_mid_recb); lamz then holds q.  Any other setter clears it.
-  bool zrecb_ok = false;
   bool external_x = false;  // x transformed by the caller (real plan): y/z passes only, no 1/N
   // long axes (n > 4096): four-step split n = n1 n2, both <= 4096 (0: a short axis).  Their
   // spectrum stays in position order p = m1 + n1 m2 for frequency m = m2 + n2 m1.
@@ -282,19 +181,6 @@ thread_local ApplyStamp g_apply_stamp;
 extern "C" void cfp_apply_stamp_clear(void) { cfp::g_apply_stamp.start = cfp::g_apply_stamp.stop = nullptr; }
 
 namespace {
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    hipGetDevice(&prev);
-    if (prev != dev) hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur;
-    hipGetDevice(&cur);
-    if (prev >= 0 && cur != prev) hipSetDevice(prev);
-  }
-};
 
 int ensure_tw(cfp_plan_s* p, int n) {
   if (p->tw.count(n)) return CFP_SUCCESS;
@@ -328,10 +214,13 @@ bool use_three_pass(const cfp_plan_s* p, bool diag_override) {
   if (!want || diag_override || p->sym_kind != 1 || p->external_x) return false;
   return three_pass_supported(p->n) || three_pass_sq_supported(p->n);
 }
-// the plan's next apply runs the recurrence P2
-bool plan_zrec(const cfp_plan_s* p) {
-  return p->zrec_ok && p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
-         three_pass_zrec_shape((int)p->n[0], p->tp_shape);
+// the one grid the recurrence kernels are built for
+bool zrec_grid(const i64 n[3]) { return n[0] == 256 && n[1] == 256 && n[2] == 256; }
+// the middle kernel of the next apply: the symbol's route where schedule and shape run a recurrence P2
+ZRoute plan_z_route(const cfp_plan_s* p) {
+  const bool rec = p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
+                   three_pass_zrec_shape((int)p->n[0], p->tp_shape);
+  return rec ? p->z_route : Z_FFT;
 }
 
 // the plane schedule (n_x = n_y in {32, 64, 100, 128}, n_z > 1): plane forward (x + y DFTs of
@@ -345,16 +234,6 @@ bool use_plane(const cfp_plan_s* p) {
   // 32^2 planes win: 32^3 at 65,300-71,500 against 39,400-43,000, profiles/r06z2_plane32_ab.txt)
   return p->schedule == CFP_SCHEDULE_AUTO && p->chunk_planes == 0 &&
          (p->n[0] == 100 || p->n[0] == 64 || p->n[0] == 32);
-}
-
-bool plan_zrec2(const cfp_plan_s* p) {
-  return p->zrec2_ok && p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
-         three_pass_zrec_shape((int)p->n[0], p->tp_shape);
-}
-
-bool plan_zrecb(const cfp_plan_s* p) {
-  return p->zrecb_ok && p->sym_kind == 1 && p->fused_axis == 2 && use_three_pass(p, false) &&
-         three_pass_zrec_shape((int)p->n[0], p->tp_shape);
 }
 
 // axis order of the 5-pass schedule: the last one is fused with the symbol
@@ -579,15 +458,21 @@ int run_apply(cfp_plan_s* p, const cd* diag_override, const cd* b, cd* x, hipStr
         e = launch_three_pass_fused(2, tn, tin, tout, a, s, p3grid);
       } else {
         a.krylov = fz != nullptr || g_apply_stamp.start != nullptr;  // an apply inside the stand-in KSP
-        if (q.tp == 1 && plan_zrec(p)) {
-          a.zrec = 1;
-          a.lamz = p->lamz;
+        switch (q.tp == 1 ? plan_z_route(p) : Z_FFT) {
+          case Z_REC_BACK:
+            a.lamz = p->lamz;
+            e = launch_three_pass_recb(tout, a, s);
+            break;
+          case Z_REC2:
+            e = launch_three_pass_rec2(tout, a, p->zrec2_tab, s);
+            break;
+          case Z_REC:
+            a.zrec = 1;
+            a.lamz = p->lamz;
+            [[fallthrough]];
+          default:
+            e = launch_three_pass(q.tp, tn, tin, tout, a, p->tp_shape, s);
         }
-        if (q.tp == 1 && plan_zrecb(p)) {
-          a.lamz = p->lamz;
-          e = launch_three_pass_recb(tout, a, s);
-        } else if (q.tp == 1 && plan_zrec2(p)) e = launch_three_pass_rec2(tout, a, p->zrec2_tab, s);
-        else e = launch_three_pass(q.tp, tn, tin, tout, a, p->tp_shape, s);
       }
       g_stamp = LaunchStamp{};
       if (e != hipSuccess) return hip_error(e, "3-sweep launch");
@@ -730,22 +615,41 @@ int upload_separable(cfp_plan_s* p, const std::vector<cd> s_nat[3]) {
   return CFP_SUCCESS;
 }
 
+// every symbol setter: no recurrence until a setter decides one (set_z_route)
+void clear_z_route(cfp_plan_s* p) { p->z_route = Z_FFT; }
+
 int set_separable(cfp_plan_s* p, const std::vector<cd> hat[3], const double lam[6]) {
   std::vector<cd> s[3];
-  for (int a = 0; a < 3; ++a) {
-    std::complex<double> l = lamc(lam, a);
-    s[a].resize(hat[a].size());
-    for (size_t k = 0; k < hat[a].size(); ++k) {
-      std::complex<double> c(hat[a][k].x, hat[a][k].y);
-      // c * lambda as in vec_kronecker_product_identity_* (src/FftLinearSolver_3D.c:100,122)
-      const double re = c.real() * l.real() - c.imag() * l.imag();
-      const double im = c.real() * l.imag() + c.imag() * l.real();
-      s[a][k] = make_cd(re, im);
-    }
-  }
+  for (int a = 0; a < 3; ++a) s[a] = transport_product(hat[a], lamc(lam, a));
   ++p->sym_version;
-  p->zrec_ok = p->zrec2_ok = p->zrecb_ok = false;
+  clear_z_route(p);
   return upload_separable(p, s);
+}
+
+// The z route of the separable symbol just uploaded (sym1d), decided at 256^3 only: lz, mz and
+// back_allowed as decide_z_route takes them.  The transport, advdiff and upwind setters end here.
+int set_z_route(cfp_plan_s* p, std::complex<double> lz, std::complex<double> mz, bool back_allowed) {
+  if (!zrec_grid(p->n)) return CFP_SUCCESS;
+  const ZDecision d = decide_z_route(p->sym1d[0], p->sym1d[1], lz, mz, back_allowed);
+  if (d.route == Z_REC2) {
+    const std::vector<cd> t = advdiff_z_table(p->sym1d[0], p->sym1d[1], lz, mz, 32);
+    if (!p->zrec2_tab) HIPCHK(hipMalloc(&p->zrec2_tab, sizeof(cd) * t.size()));
+    HIPCHK(hipMemcpy(p->zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
+  }
+  p->z_route = d.route;
+  p->lamz = make_cd(d.lamz.real(), d.lamz.imag());
+  return CFP_SUCCESS;
+}
+
+// the advection-diffusion tables of (lam, mu) in closed form (set_separable's product with lambda
+// is folded in) and their z route
+int set_advdiff(cfp_plan_s* p, const double lam[6], const double mu[6], bool back_allowed) {
+  DeviceGuard dg(p->device);
+  const AxisTables s = axis_symbols(p->n, lam, mu);
+  ++p->sym_version;
+  clear_z_route(p);
+  int rc = upload_separable(p, s.data());
+  return rc ? rc : set_z_route(p, lamc(lam, 2), lamc(mu, 2), back_allowed);
 }
 
 
@@ -849,88 +753,47 @@ extern "C" int cfp_plan_set_symbol_transport(cfp_plan_t p, const double lam[6]) 
   std::vector<cd> hat[3];
   for (int a = 0; a < 3; ++a) hat[a] = host_transport_symbol(p->n[a]);
   int rc = set_separable(p, hat, lam);
-  if (rc) return rc;
-  if (p->n[0] == 256 && p->n[1] == 256 && p->n[2] == 256) {  // the one grid k_tp_mid_rec is built for
-    const std::complex<double> lz = lamc(lam, 2);
-    p->zrec_amax = transport_z_ratio(p->sym1d[0], p->sym1d[1], lz);
-    p->zrec_ok = p->zrec_amax <= kZrecMaxRatio;
-    p->lamz = make_cd(lz.real(), lz.imag());
-  }
-  return CFP_SUCCESS;
+  // first order along z on set_separable's own tables: k_tp_mid_rec or the FFT kernel
+  return rc ? rc : set_z_route(p, lamc(lam, 2), 0.0, false);
 }
 
 extern "C" int cfp_plan_mid_kernel(cfp_plan_t p, int* kind) {
   if (!p || !kind) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  *kind = plan_zrec(p) ? CFP_MID_KERNEL_ZREC
-                       : (plan_zrecb(p) ? CFP_MID_KERNEL_ZREC_BACK
-                                        : (plan_zrec2(p) ? CFP_MID_KERNEL_ZREC2 : CFP_MID_KERNEL_FFT));
+  *kind = plan_z_route(p);
   return CFP_SUCCESS;
 }
 
 extern "C" int cfp_plan_set_symbol_advdiff(cfp_plan_t p, const double lam[6], const double mu[6]) {
   if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  DeviceGuard dg(p->device);
-  // the separable tables in closed form (set_separable's product with lambda is folded in)
-  std::vector<cd> s[3];
-  for (int a = 0; a < 3; ++a) s[a] = host_advdiff_symbol(p->n[a], lamc(lam, a), lamc(mu, a));
-  ++p->sym_version;
-  p->zrec_ok = p->zrec2_ok = p->zrecb_ok = false;
-  int rc = upload_separable(p, s);
-  if (rc) return rc;
-  if (p->n[0] == 256 && p->n[1] == 256 && p->n[2] == 256) {  // the one grid the recurrence kernels are built for
-    const std::complex<double> lz = lamc(lam, 2), mz = lamc(mu, 2);
-    if (mz == 0.0) {
-      // first order along z: k_tp_mid_rec, which reads c from the column table
-      p->zrec_amax = transport_z_ratio(p->sym1d[0], p->sym1d[1], lz);
-      p->zrec_ok = p->zrec_amax <= kZrecMaxRatio;
-      p->lamz = make_cd(lz.real(), lz.imag());
-    } else {
-      double r[2];
-      advdiff_z_ratio(p->sym1d[0], p->sym1d[1], lz, mz, r);
-      if (r[0] <= kZrec2MaxRatio && r[1] <= kZrec2MaxRatio) {
-        const std::vector<cd> t = advdiff_z_table(p->sym1d[0], p->sym1d[1], lz, mz, 32);
-        if (!p->zrec2_tab) HIPCHK(hipMalloc(&p->zrec2_tab, sizeof(cd) * t.size()));
-        HIPCHK(hipMemcpy(p->zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
-        p->zrec2_ok = true;
-      }
-    }
-  }
-  return CFP_SUCCESS;
+  return set_advdiff(p, lam, mu, false);
 }
 
 extern "C" int cfp_upwind_to_advdiff(const double lam[6], const double mu[6], double lam_out[6], double mu_out[6]) {
   if (!lam || !mu || !lam_out || !mu_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  // |lam| (1 - conj w) + mu (2 - w - conj w) = lam (1 - w) + (mu - lam) (2 - w - conj w) for lam < 0
-  for (int a = 0; a < 3; ++a) {
-    const bool neg = lam[2 * a] < 0.0;
-    for (int c = 0; c < 2; ++c) {
-      const double l = lam[2 * a + c], m = mu[2 * a + c];
-      lam_out[2 * a + c] = l;
-      mu_out[2 * a + c] = neg ? m - l : m;
-    }
-  }
+  upwind_to_advdiff(2, lam, mu, lam_out, mu_out);
   return CFP_SUCCESS;
 }
 
 extern "C" int cfp_plan_set_symbol_upwind(cfp_plan_t p, const double lam[6], const double mu[6]) {
   if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  // the tables and the route of the mapped pair; pure upwind transport against z may run backwards
   double l2[6], m2[6];
-  cfp_upwind_to_advdiff(lam, mu, l2, m2);
-  // the tables, the version bump, the dropped graphs and the zrec / zrec2 routing of the mapped pair
-  int rc = cfp_plan_set_symbol_advdiff(p, l2, m2);
-  if (rc) return rc;
-  const std::complex<double> lz = lamc(lam, 2), mz = lamc(mu, 2);
-  if (p->n[0] == 256 && p->n[1] == 256 && p->n[2] == 256 && lz.real() < 0.0 && mz == 0.0) {
-    // pure upwind transport against z: first order towards z + 1.  The mapped pair has p = 0 and
-    // q = -lamz, so its ratios (advdiff_z_ratio) are a = 0 and b = q / (c + q): the backward
-    // recurrence under k_tp_mid_rec's cap, else the FFT kernel (never the two-sided one)
-    double r[2];
-    advdiff_z_ratio(p->sym1d[0], p->sym1d[1], lz, -lz, r);
-    p->zrec2_ok = false;
-    p->zrec_amax = r[1];
-    p->zrecb_ok = r[1] <= kZrecMaxRatio;
-    p->lamz = make_cd(-lz.real(), -lz.imag());
-  }
+  upwind_to_advdiff(2, lam, mu, l2, m2);
+  return set_advdiff(p, l2, m2, upwind_back(lamc(lam, 2), lamc(mu, 2)));
+}
+
+extern "C" int cfp_symbol_z_route(int64_t nx, int64_t ny, int64_t nz, const double lam[6], const double mu[6],
+                                  int upwind, int* kind, double ratios[2]) {
+  if (!lam || !mu || !kind || !ratios) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  if (nx < 1 || ny < 1 || nz < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
+  double l2[6], m2[6];  // what cfp_plan_set_symbol_upwind sets
+  if (upwind) upwind_to_advdiff(2, lam, mu, l2, m2);
+  const double* m = upwind ? m2 : mu;
+  const i64 n[3] = {nx, ny, nz};
+  const AxisTables s = axis_symbols(n, lam, m);
+  const ZDecision d = decide_z_route(s[0], s[1], lamc(lam, 2), lamc(m, 2), upwind && upwind_back(lamc(lam, 2), lamc(mu, 2)));
+  *kind = zrec_grid(n) ? d.route : Z_FFT;
+  std::memcpy(ratios, d.ratios, sizeof(d.ratios));
   return CFP_SUCCESS;
 }
 
@@ -955,13 +818,8 @@ extern "C" int cfp_advdiff_z_ratio(int64_t nx, int64_t ny, const double lam[6], 
 extern "C" int cfp_transport_z_ratio(int64_t nx, int64_t ny, const double lam[6], double* amax) {
   if (!lam || !amax) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
   if (nx < 1 || ny < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "grid sizes must be >= 1");
-  std::vector<cd> s[2] = {host_transport_symbol(nx), host_transport_symbol(ny)};
-  for (int a = 0; a < 2; ++a)
-    for (cd& v : s[a]) {
-      const std::complex<double> t = std::complex<double>(v.x, v.y) * lamc(lam, a);
-      v = make_cd(t.real(), t.imag());
-    }
-  *amax = transport_z_ratio(s[0], s[1], lamc(lam, 2));
+  *amax = transport_z_ratio(transport_product(host_transport_symbol(nx), lamc(lam, 0)),
+                            transport_product(host_transport_symbol(ny), lamc(lam, 1)), lamc(lam, 2));
   return CFP_SUCCESS;
 }
 
@@ -984,7 +842,7 @@ extern "C" int cfp_plan_set_diag(cfp_plan_t p, const double* diag, int on_device
   DeviceGuard dg(p->device);
   free_symbol(p);
   ++p->sym_version;
-  p->zrec_ok = p->zrec2_ok = p->zrecb_ok = false;
+  clear_z_route(p);
   HIPCHK(hipMalloc(&p->diag, sizeof(cd) * (size_t)p->N));
   HIPCHK(hipMemcpy(p->diag, diag, sizeof(cd) * (size_t)p->N, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
   p->sym_kind = 2;

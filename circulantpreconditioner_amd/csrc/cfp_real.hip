@@ -176,25 +176,13 @@ static bool use_three(const cfp_rplan_s* p) { return three_ok(p) && p->schedule 
 // 5,623-5,693 real PCApply/s (+10.0 to +10.9 %; spread inside a variant <= 0.2 %).
 constexpr bool kRealRec2Auto = true;
 // the next apply's half-spectrum stage is the two-sided z recurrence
+static bool rec2_grid(const cfp_rplan_s* p) { return three_ok(p) && p->n[0] == 256; }
 static bool use_zrec2(const cfp_rplan_s* p) {
-  return use_three(p) && p->n[0] == 256 && p->zrec2_ok && p->mid != CFP_RMID_FFT &&
+  return use_three(p) && rec2_grid(p) && p->zrec2_ok && p->mid != CFP_RMID_FFT &&
          (p->mid == CFP_RMID_REC || kRealRec2Auto);
 }
 
 namespace {
-struct RGuard {
-  int prev = -1;
-  explicit RGuard(int dev) {
-    hipGetDevice(&prev);
-    if (prev != dev) hipSetDevice(dev);
-  }
-  ~RGuard() {
-    int cur;
-    hipGetDevice(&cur);
-    if (prev >= 0 && cur != prev) hipSetDevice(prev);
-  }
-};
-
 void free_rplan(cfp_rplan_s* p) {
   if (p->main) cfp_plan_destroy(p->main);
   if (p->nyq) cfp_plan_destroy(p->nyq);
@@ -211,8 +199,13 @@ void free_rplan(cfp_rplan_s* p) {
   delete p;
 }
 
-// the 3-sweep schedule's tables (allocated with the first symbol)
-int upload_three(cfp_rplan_s* p, const std::vector<cd>& col, const std::vector<cd>& colq, const std::vector<cd>& ax) {
+// the 3-sweep schedule's tables from the axes' parts s (allocated with the first symbol): colsym3
+// over the half spectrum kx < M, colsymq the Nyquist column kx = M, axsym3 = s_z
+int upload_three(cfp_rplan_s* p, const std::vector<cd> s[3]) {
+  DeviceGuard g(p->device);
+  const i64 M = p->M, ny = p->n[1];
+  const std::vector<cd> col = column_sums(s[0], 0, M, s[1], 0, ny, M), colq = column_sums(s[0], M, 1, s[1], 0, ny, 1);
+  const std::vector<cd>& ax = s[2];
   if (!p->colsym3) HIPCHK(hipMalloc(&p->colsym3, sizeof(cd) * col.size()));
   if (!p->axsym3) HIPCHK(hipMalloc(&p->axsym3, sizeof(cd) * ax.size()));
   if (!p->colsymq) HIPCHK(hipMalloc(&p->colsymq, sizeof(cd) * colq.size()));
@@ -309,7 +302,7 @@ extern "C" int cfp_rplan_create(cfp_rplan_t* plan, int64_t nx, int64_t ny, int64
     free_rplan(p);
     return rc;
   }
-  RGuard g(device);
+  DeviceGuard g(device);
   std::vector<cd> tw = host_twiddles((int)nx, -1);
   hipError_t e = hipMalloc(&p->H, sizeof(cd) * (size_t)(M * ny * nz));
   if (e == hipSuccess) e = hipMalloc(&p->Q, sizeof(cd) * (size_t)(ny * nz));
@@ -325,7 +318,7 @@ extern "C" int cfp_rplan_create(cfp_rplan_t* plan, int64_t nx, int64_t ny, int64
 
 extern "C" int cfp_rplan_destroy(cfp_rplan_t p) {
   if (!p) return CFP_SUCCESS;
-  RGuard g(p->device);
+  DeviceGuard g(p->device);
   free_rplan(p);
   return CFP_SUCCESS;
 }
@@ -341,19 +334,12 @@ extern "C" int cfp_rplan_set_symbol_transport(cfp_rplan_t p, const double lam[3]
   CFPCHK(cfp_plan_set_symbol_separable(p->nyq, (const double*)&hx[(size_t)p->M], (const double*)hy.data(),
                                        (const double*)hz.data(), lam6));
   if (three_ok(p)) {  // the 3-sweep tables: colsym [kx + M ky] = lx hx[kx] + ly hy[ky], axsym = lz hz
-    RGuard g(p->device);
-    const i64 M = p->M, ny = p->n[1], nz = p->n[2];
-    std::vector<cd> col((size_t)(M * ny)), ax((size_t)nz);
-    for (i64 ky = 0; ky < ny; ++ky)
-      for (i64 kx = 0; kx < M; ++kx)
-        col[(size_t)(kx + M * ky)] = make_cd(lam[0] * hx[(size_t)kx].x + lam[1] * hy[(size_t)ky].x,
-                                             lam[0] * hx[(size_t)kx].y + lam[1] * hy[(size_t)ky].y);
-    for (i64 kz = 0; kz < nz; ++kz) ax[(size_t)kz] = make_cd(lam[2] * hz[(size_t)kz].x, lam[2] * hz[(size_t)kz].y);
-    std::vector<cd> colq((size_t)ny);  // the Nyquist column kx = M
-    for (i64 ky = 0; ky < ny; ++ky)
-      colq[(size_t)ky] = make_cd(lam[0] * hx[(size_t)M].x + lam[1] * hy[(size_t)ky].x,
-                                 lam[0] * hx[(size_t)M].y + lam[1] * hy[(size_t)ky].y);
-    CFPCHK(upload_three(p, col, colq, ax));
+    // (a real scale of each axis, not transport_product: the sign of a zero may differ)
+    const std::vector<cd>* h[3] = {&hx, &hy, &hz};
+    std::vector<cd> s[3];
+    for (int a = 0; a < 3; ++a)
+      for (const cd& v : *h[a]) s[a].push_back(make_cd(lam[a] * v.x, lam[a] * v.y));
+    CFPCHK(upload_three(p, s));
   }
   p->zrec2_ok = false;
   p->has_sym = true;
@@ -363,8 +349,8 @@ extern "C" int cfp_rplan_set_symbol_transport(cfp_rplan_t p, const double lam[3]
 extern "C" int cfp_rplan_set_symbol_advdiff(cfp_rplan_t p, const double lam[3], const double mu[3]) {
   if (!p || !lam || !mu) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
   // the axes' parts in closed form, lambda and mu folded in (unit weights below)
-  std::vector<cd> s[3];
-  for (int a = 0; a < 3; ++a) s[a] = host_advdiff_symbol(p->n[a], {lam[a], 0.0}, {mu[a], 0.0});
+  const double lam6[6] = {lam[0], 0.0, lam[1], 0.0, lam[2], 0.0}, mu6[6] = {mu[0], 0.0, mu[1], 0.0, mu[2], 0.0};
+  const AxisTables s = axis_symbols(p->n, lam6, mu6);
   const double one6[6] = {1.0, 0.0, 1.0, 0.0, 1.0, 0.0};
   // half spectrum kx < nx/2, and the Nyquist column kx = nx/2
   CFPCHK(cfp_plan_set_symbol_separable(p->main, (const double*)s[0].data(), (const double*)s[1].data(),
@@ -373,28 +359,17 @@ extern "C" int cfp_rplan_set_symbol_advdiff(cfp_rplan_t p, const double lam[3], 
                                        (const double*)s[2].data(), one6));
   p->zrec2_ok = false;
   if (three_ok(p)) {  // the 3-sweep tables: colsym [kx + M ky] = s_x[kx] + s_y[ky], axsym = s_z
-    RGuard g(p->device);
-    const i64 M = p->M, ny = p->n[1];
-    std::vector<cd> col((size_t)(M * ny)), colq((size_t)ny);
-    for (i64 ky = 0; ky < ny; ++ky) {
-      for (i64 kx = 0; kx < M; ++kx)
-        col[(size_t)(kx + M * ky)] =
-            make_cd(s[0][(size_t)kx].x + s[1][(size_t)ky].x, s[0][(size_t)kx].y + s[1][(size_t)ky].y);
-      colq[(size_t)ky] = make_cd(s[0][(size_t)M].x + s[1][(size_t)ky].x, s[0][(size_t)M].y + s[1][(size_t)ky].y);
-    }
-    CFPCHK(upload_three(p, col, colq, s[2]));
-    if (p->n[0] == 256 && mu[2] != 0.0) {  // the one grid k_tp_mid_rec2_half is built for
-      // real lambda, mu: a half-spectrum column and its mirror have conjugate factors, so the
-      // full grid's ratios are the half's
-      double r[2];
-      advdiff_z_ratio(s[0], s[1], {lam[2], 0.0}, {mu[2], 0.0}, r);
-      if (r[0] <= kZrec2MaxRatio && r[1] <= kZrec2MaxRatio) {
-        const std::vector<cd> t = advdiff_z_table(s[0], s[1], {lam[2], 0.0}, {mu[2], 0.0}, (int)(M / 8));
-        if (t.size() != (size_t)kRealRec2TabLen) return set_error(CFP_ERR_LIB, "recurrence table size");
-        if (!p->zrec2_tab) HIPCHK(hipMalloc(&p->zrec2_tab, sizeof(cd) * t.size()));
-        HIPCHK(hipMemcpy(p->zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
-        p->zrec2_ok = true;
-      }
+    CFPCHK(upload_three(p, s.data()));
+    // real lambda, mu: a half-spectrum column and its mirror have conjugate factors, so the
+    // full grid's ratios are the half's
+    const std::complex<double> lz(lam[2], 0.0), mz(mu[2], 0.0);
+    if (rec2_grid(p) && decide_z_route(s[0], s[1], lz, mz, false).route == Z_REC2) {
+      DeviceGuard g(p->device);
+      const std::vector<cd> t = advdiff_z_table(s[0], s[1], lz, mz, (int)(p->M / 8));
+      if (t.size() != (size_t)kRealRec2TabLen) return set_error(CFP_ERR_LIB, "recurrence table size");
+      if (!p->zrec2_tab) HIPCHK(hipMalloc(&p->zrec2_tab, sizeof(cd) * t.size()));
+      HIPCHK(hipMemcpy(p->zrec2_tab, t.data(), sizeof(cd) * t.size(), hipMemcpyHostToDevice));
+      p->zrec2_ok = true;
     }
   }
   p->has_sym = true;
@@ -406,10 +381,7 @@ extern "C" int cfp_rplan_set_symbol_upwind(cfp_rplan_t p, const double lam[3], c
   // cfp_upwind_to_advdiff on real numbers; the tables, the routing and what the plan remembers
   // are the mapped pair's
   double l2[3], m2[3];
-  for (int a = 0; a < 3; ++a) {
-    l2[a] = lam[a];
-    m2[a] = lam[a] < 0.0 ? mu[a] - lam[a] : mu[a];
-  }
+  upwind_to_advdiff(1, lam, mu, l2, m2);
   return cfp_rplan_set_symbol_advdiff(p, l2, m2);
 }
 
@@ -446,7 +418,7 @@ extern "C" int cfp_rplan_schedule(cfp_rplan_t p, int* three) {
 
 extern "C" int cfp_rplan_apply(cfp_rplan_t p, const double* b, double* x, void* stream) {
   if (!p || !b || !x) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  RGuard g(p->device);
+  DeviceGuard g(p->device);
   return run_real(p, b, x, (hipStream_t)stream, nullptr);
 }
 
@@ -460,7 +432,7 @@ extern "C" int cfp_rplan_time_passes(cfp_rplan_t p, const double* b, double* x, 
                                      void* stream) {
   if (!p || !b || !x || !ms_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
   if (iters < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "iters must be >= 1");
-  RGuard g(p->device);
+  DeviceGuard g(p->device);
   hipStream_t s = (hipStream_t)stream;
   std::vector<hipEvent_t> ev(5);
   for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));

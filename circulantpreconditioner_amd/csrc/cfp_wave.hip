@@ -54,19 +54,6 @@ struct cfp_wave_plan_s {
 
 namespace {
 
-struct Guard {
-  int prev = -1;
-  explicit Guard(int dev) {
-    hipGetDevice(&prev);
-    if (prev != dev) hipSetDevice(dev);
-  }
-  ~Guard() {
-    int cur;
-    hipGetDevice(&cur);
-    if (prev >= 0 && cur != prev) hipSetDevice(prev);
-  }
-};
-
 int ensure_tw(cfp_wave_plan_s* p, int n) {
   if (p->tw.count(n)) return CFP_SUCCESS;
   std::vector<cd> h = host_twiddles(n, -1);
@@ -214,7 +201,7 @@ extern "C" int cfp_wave_plan_create_dim(cfp_wave_plan_t* plan, int64_t nx, int64
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return set_error(CFP_ERR_ARG_OUTOFRANGE, "device %d out of range", device);
-  Guard g(device);
+  DeviceGuard g(device);
   std::unique_ptr<cfp_wave_plan_s> p(new cfp_wave_plan_s);
   p->device = device;
   p->n[0] = nx;
@@ -240,7 +227,7 @@ extern "C" int cfp_wave_plan_create(cfp_wave_plan_t* plan, int64_t nx, int64_t n
 
 extern "C" int cfp_wave_plan_destroy(cfp_wave_plan_t p) {
   if (!p) return CFP_SUCCESS;
-  Guard g(p->device);
+  DeviceGuard g(p->device);
   for (auto& kv : p->tw) hipFree(kv.second);
   for (int a = 0; a < 3; ++a)
     if (p->tab[a]) hipFree(p->tab[a]);
@@ -255,7 +242,7 @@ extern "C" int cfp_wave_plan_set_symbol(cfp_wave_plan_t p, const double kappa[3]
   if (!(c0 > 0.0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "c0 must be > 0");
   for (int a = 0; a < 3; ++a)
     if (!(kappa[a] >= 0.0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "kappa must be >= 0");
-  Guard g(p->device);
+  DeviceGuard g(p->device);
   for (int a = 0; a < 3; ++a) {
     const i64 n = p->n[a];
     std::vector<double2> t((size_t)n);
@@ -274,7 +261,7 @@ extern "C" int cfp_wave_plan_set_symbol(cfp_wave_plan_t p, const double kappa[3]
 
 extern "C" int cfp_wave_plan_apply(cfp_wave_plan_t p, const double* b, double* x, void* stream) {
   if (!p || !b || !x) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  Guard g(p->device);
+  DeviceGuard g(p->device);
   return run_wave(p, (const cd*)b, (cd*)x, (hipStream_t)stream, nullptr);
 }
 
@@ -286,7 +273,7 @@ extern "C" int cfp_wave_plan_apply_dots(cfp_wave_plan_t p, const double* b, doub
   if (!p || !b || !x || (nv > 0 && (!v || !dots))) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
   if (nv < 0 || nv > 8) return set_error(CFP_ERR_ARG_OUTOFRANGE, "nv must be in 0..8");
   if (fused) *fused = 0;
-  Guard g(p->device);
+  DeviceGuard g(p->device);
   hipStream_t s = (hipStream_t)stream;
   if (nv == 0) return run_wave(p, (const cd*)b, (cd*)x, s, nullptr);
   if (use_three(p) && nv <= 4) {
@@ -318,13 +305,13 @@ extern "C" int cfp_wave_plan_apply_dots(cfp_wave_plan_t p, const double* b, doub
 
 extern "C" int cfp_wave_plan_forward(cfp_wave_plan_t p, const double* in, double* out, void* stream) {
   if (!p || !in || !out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  Guard g(p->device);
+  DeviceGuard g(p->device);
   return run_transform(p, false, (const cd*)in, (cd*)out, (hipStream_t)stream);
 }
 
 extern "C" int cfp_wave_plan_backward(cfp_wave_plan_t p, const double* in, double* out, void* stream) {
   if (!p || !in || !out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  Guard g(p->device);
+  DeviceGuard g(p->device);
   return run_transform(p, true, (const cd*)in, (cd*)out, (hipStream_t)stream);
 }
 
@@ -349,7 +336,7 @@ extern "C" int cfp_wave_plan_time_passes(cfp_wave_plan_t p, const double* b, dou
                                          void* stream) {
   if (!p || !b || !x || !ms_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
   if (iters < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "iters must be >= 1");
-  Guard g(p->device);
+  DeviceGuard g(p->device);
   hipStream_t s = (hipStream_t)stream;
   const size_t np = wave_steps(p).size();
   std::vector<double> acc(np, 0.0);

@@ -377,6 +377,16 @@ def advdiff_z_ratio(nx: int, ny: int, lam: Sequence, mu: Sequence) -> tuple:
     return float(r[0]), float(r[1])
 
 
+def z_route(dims: Sequence, lam: Sequence, mu: Sequence = (0, 0, 0), upwind: bool = False) -> tuple:
+    """(kind, (ra, rb)): the middle kernel -- CirculantPlan.mid_kernel()'s names -- a plan of grid
+    `dims` under the default schedule and shape launches after set_advdiff_symbol(lam, mu), or
+    after set_upwind_symbol(lam, mu) with upwind=True, and the z ratios decided on; no GPU needed."""
+    k, r = ctypes.c_int(), (ctypes.c_double * 2)()
+    nx, ny, nz = (int(v) for v in dims)
+    check(lib().cfp_symbol_z_route(nx, ny, nz, _lam6(lam), _lam6(mu), int(bool(upwind)), ctypes.byref(k), r))
+    return {1: "zrec", 2: "zrec2", 3: "zrecb"}.get(k.value, "fft"), (float(r[0]), float(r[1]))
+
+
 def pointwise_divide(w: torch.Tensor, x: torch.Tensor, y: torch.Tensor, stream=None) -> torch.Tensor:
     n = w.numel()
     check(lib().cfp_pointwise_divide(_dev_ptr(w, n, "w"), _dev_ptr(x, n, "x"), _dev_ptr(y, n, "y"), n,

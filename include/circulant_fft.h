@@ -261,6 +261,13 @@ int cfp_advdiff_symbol_1d(int64_t n, const double lam[2], const double mu[2], do
  * first-order recurrence.  ratios_host = {max |a|, max |b|} over the columns; infinity where
  * beta is 0. */
 int cfp_advdiff_z_ratio(int64_t nx, int64_t ny, const double lam[6], const double mu[6], double ratios_host[2]);
+/* host (no GPU needed): the middle kernel (CFP_MID_KERNEL_*, the rule at cfp_plan_mid_kernel) that
+ * a plan of this grid under the default schedule and shape launches for the symbol of
+ * cfp_plan_set_symbol_advdiff(lam, mu), or with upwind != 0 of cfp_plan_set_symbol_upwind(lam, mu),
+ * and the ratios it was decided on: {cfp_transport_z_ratio, 0} for mu_z == 0, cfp_advdiff_z_ratio
+ * of the (mapped) pair otherwise.  Any grid but 256^3 gives CFP_MID_KERNEL_FFT. */
+int cfp_symbol_z_route(int64_t nx, int64_t ny, int64_t nz, const double lam[6], const double mu[6], int upwind,
+                       int *kind, double ratios_host[2]);
 
 #ifdef __cplusplus
 }
