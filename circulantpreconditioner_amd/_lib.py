@@ -1,4 +1,5 @@
-"""ctypes binding of ``libcirculant_fft.so`` (the HIP/gfx950 library).
+"""Loading of ``libcirculant_fft.so`` (the HIP/gfx950 library) and of its real-scalar build
+``libcirculant_fft_real.so``; the signatures are the one table of ``_lib_ext.py``.
 
 There is no fallback: if the shared library is missing or fails to load, every
 entry point raises.  Build it with ``__graft_entry__.build()`` or
@@ -10,11 +11,9 @@ import ctypes
 import os
 import threading
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libcirculant_fft.so")
+from ._lib_ext import COMPLEX_BUILD, REAL_BUILD, PetscScalar, declare
 
-_lock = threading.Lock()
-_lib = None
+_HERE = os.path.dirname(os.path.abspath(__file__))
 
 # error codes (petscerror.h values), include/circulant_fft.h
 CFP_SUCCESS = 0
@@ -26,80 +25,39 @@ class CirculantError(RuntimeError):
         self.code = code
 
 
-def _declare(L) -> None:
-    i64, u64, dp, vp, c_int = ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int
-    P = ctypes.POINTER
-    sig = {
-        "cfp_version": ([], ctypes.c_char_p),
-        "cfp_last_error": ([], ctypes.c_char_p),
-        "cfp_device_count": ([P(c_int)], c_int),
-        "cfp_stream_sync": ([vp], c_int),
-        "cfp_device_copy": ([vp, vp, ctypes.c_size_t, vp], c_int),
-        "cfp_plan_create": ([P(vp), i64, i64, i64, c_int], c_int),
-        "cfp_plan_destroy": ([vp], c_int),
-        "cfp_plan_set_symbol_transport": ([vp, dp], c_int),
-        "cfp_plan_set_symbol_separable": ([vp, dp, dp, dp, dp], c_int),
-        "cfp_plan_set_diag": ([vp, dp, c_int], c_int),
-        "cfp_plan_get_diag": ([vp, dp, vp], c_int),
-        "cfp_plan_symbol_version": ([vp, P(u64)], c_int),
-        "cfp_plan_apply": ([vp, dp, dp, vp], c_int),
-        "cfp_plan_apply_ex": ([vp, dp, dp, vp, vp], c_int),
-        "cfp_plan_apply_with_diag": ([vp, dp, dp, dp, vp], c_int),
-        "cfp_plan_apply_host": ([vp, dp, dp], c_int),
-        "cfp_plan_apply_with_diag_host": ([vp, dp, dp, dp], c_int),
-        "cfp_plan_forward": ([vp, dp, dp, vp], c_int),
-        "cfp_plan_backward": ([vp, dp, dp, vp], c_int),
-        "cfp_plan_set_chunking": ([vp, i64], c_int),
-        "cfp_plan_set_graph": ([vp, c_int], c_int),
-        "cfp_plan_set_schedule": ([vp, c_int], c_int),
-        "cfp_plan_set_three_pass_shape": ([vp, c_int, c_int], c_int),
-        "cfp_rplan_create": ([P(vp), i64, i64, i64, c_int], c_int),
-        "cfp_rplan_destroy": ([vp], c_int),
-        "cfp_rplan_set_symbol_transport": ([vp, P(ctypes.c_double)], c_int),
-        "cfp_rplan_set_symbol_advdiff": ([vp, P(ctypes.c_double), P(ctypes.c_double)], c_int),
-        "cfp_rplan_set_symbol_upwind": ([vp, P(ctypes.c_double), P(ctypes.c_double)], c_int),
-        "cfp_rplan_set_mid_kernel": ([vp, c_int], c_int),
-        "cfp_rplan_mid_kernel": ([vp, P(c_int)], c_int),
-        "cfp_rplan_apply": ([vp, vp, vp, vp], c_int),
-        "cfp_rplan_num_passes": ([vp, P(c_int)], c_int),
-        "cfp_rplan_time_passes": ([vp, vp, vp, c_int, P(ctypes.c_double), vp], c_int),
-        "cfp_rplan_set_schedule": ([vp, c_int], c_int),
-        "cfp_rplan_schedule": ([vp, P(c_int)], c_int),
-        "cfp_plan_num_passes": ([vp, P(c_int)], c_int),
-        "cfp_plan_pass_info": ([vp, c_int, P(c_int), P(c_int), P(i64), P(c_int), P(c_int)], c_int),
-        "cfp_plan_time_passes": ([vp, dp, dp, c_int, dp, vp], c_int),
-        "cfp_plan_profile_begin": ([vp, c_int, c_int], c_int),
-        "cfp_plan_profile_end": ([vp, dp, ctypes.POINTER(c_int)], c_int),
-        "cfp_pointwise_divide": ([dp, dp, dp, i64, vp], c_int),
-        "cfp_scale": ([dp, ctypes.c_double, ctypes.c_double, i64, vp], c_int),
-        "cfp_fill_uniform": ([dp, i64, u64, i64, vp], c_int),
-        "cfp_build_diag_3d": ([dp, dp, dp, dp, i64, i64, i64, dp, vp], c_int),
-        "cfp_transport_symbol_1d": ([i64, dp], c_int),
-    }
-    for name, (args, res) in sig.items():
-        fn = getattr(L, name)
-        fn.argtypes = args
-        fn.restype = res
-    # optional groups (declared in include/circulant_fft_dist.h, include/pcshell_fft3d.h)
-    from . import _lib_ext
-    _lib_ext.declare(L)
+class _Library:
+    """One of the two shared libraries: loaded on the first call, under its lock, with every
+    signature of the table (_lib_ext.signatures) that its build holds.  `path` is read at that
+    first call (a function: the module-level LIB_PATH / REAL_LIB_PATH as it then stands, so a tool
+    may point it at another build before anything is loaded).  Raises if the file is missing:
+    there is no CPU fallback."""
+
+    def __init__(self, path, mode: int, build: str, hint: str):
+        self._path, self._mode, self._build, self._hint = path, mode, build, hint
+        self._lock = threading.Lock()
+        self._lib = None
+
+    def __call__(self):
+        if self._lib is None:
+            with self._lock:
+                if self._lib is None:
+                    path = self._path()
+                    if not os.path.exists(path):
+                        raise ImportError(f"{os.path.basename(path)} not found at {path}; build it with {self._hint}")
+                    L = ctypes.CDLL(path, mode=self._mode)
+                    declare(L, PetscScalar if self._build == COMPLEX_BUILD else ctypes.c_double, self._build)
+                    self._lib = L
+        return self._lib
 
 
-def lib():
-    """Load the HIP library (raises if it is missing: there is no CPU fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is None:
-            if not os.path.exists(LIB_PATH):
-                raise ImportError(
-                    f"libcirculant_fft.so not found at {LIB_PATH}; build it with "
-                    "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
-            L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-            _declare(L)
-            _lib = L
-    return _lib
+LIB_PATH = os.path.join(_HERE, "lib", "libcirculant_fft.so")
+REAL_LIB_PATH = os.path.join(_HERE, "lib", "libcirculant_fft_real.so")
+
+# the complex library is RTLD_GLOBAL; the real-scalar one is RTLD_LOCAL (and linked -Bsymbolic), so
+# that both live in one process
+lib = _Library(lambda: LIB_PATH, ctypes.RTLD_GLOBAL, COMPLEX_BUILD,
+               "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
+real_lib = _Library(lambda: REAL_LIB_PATH, ctypes.RTLD_LOCAL, REAL_BUILD, "`make -C circulantpreconditioner_amd/csrc`")
 
 
 def check(rc: int) -> None:

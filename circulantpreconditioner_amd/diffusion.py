@@ -4,8 +4,8 @@ csrc/diffusion_cartesian.cpp).  The mirror of transport.py for the operator the 
 list asks for next.
 
 Both libraries hold these functions.  The default is the complex-scalar one; ``real=True`` runs
-the real-scalar library (petsc_real.py: PetscScalar = double, fields of N doubles, the real-data
-plan behind the PCSHELL).
+the real-scalar library (PetscScalar = double, fields of N doubles, the real-data plan behind the
+PCSHELL).  Each function picks its binding (_boundary.COMPLEX or REAL) once and runs one body.
 """
 from __future__ import annotations
 
@@ -14,9 +14,8 @@ from typing import Sequence
 
 import numpy as np
 
-from ._lib import check, lib
-from ._lib_ext import AdvDiffConfig, AdvDiffResult, PetscScalar, StructuredDiffusionContext
-from .petsc import PETSC_COMM_SELF, Mat, PetscCall, Vec
+from ._boundary import COMPLEX, PETSC_COMM_SELF, REAL
+from ._lib_ext import AdvDiffConfig, AdvDiffResult
 
 BC_WALL, BC_PERIODIC = 0, 1
 PC_NONE, PC_FFT, PC_FFT_UPWIND = 0, 1, 2
@@ -29,16 +28,18 @@ def _d3(v) -> ctypes.Array:
     return (ctypes.c_double * 3)(*[float(x) for x in v])
 
 
-def _real_lib():
-    from . import petsc_real
-    return petsc_real
+def _binding(real: bool):
+    return REAL if real else COMPLEX
 
 
 def advdiff_csr(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[float], nu: float,
                 bc: str | int = "wall", shift: float = 0.0, real: bool = False):
     """(rowptr, col, val) of shift*I + dt (a . grad - nu lap) on the grid (host only): upwind
     advection with the conservative sign plus the centred 7-point diffusion; bc 'wall' skips the
-    border faces, 'periodic' gives the circulant the FFT preconditioner inverts."""
+    border faces, 'periodic' gives the circulant the FFT preconditioner inverts.  Bad arguments
+    raise CirculantError with the library's message from either library (real=True used to raise a
+    bare ValueError, when the real-scalar module had no check())."""
+    B = _binding(real)
     nx, ny, nz = (int(v) for v in dims)
     n = nx * ny * nz
     b = _BC[bc] if isinstance(bc, str) else int(bc)
@@ -47,12 +48,9 @@ def advdiff_csr(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[
     val = np.empty(7 * n, dtype=np.complex128)
     nnz = ctypes.c_int64()
     P64 = ctypes.POINTER(ctypes.c_int64)
-    fn = _real_lib().lib().cfp_advdiff_csr if real else lib().cfp_advdiff_csr
-    rc = fn(nx, ny, nz, _d3(h), float(dt), _d3(a), float(nu), b, float(shift), rowptr.ctypes.data_as(P64),
-            col.ctypes.data_as(P64), val.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(nnz))
-    if rc and real:
-        raise ValueError(f"cfp_advdiff_csr: bad arguments (code {rc})")
-    check(rc)
+    B.check(B.lib().cfp_advdiff_csr(nx, ny, nz, _d3(h), float(dt), _d3(a), float(nu), b, float(shift),
+                                    rowptr.ctypes.data_as(P64), col.ctypes.data_as(P64),
+                                    val.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(nnz)))
     k = nnz.value
     return rowptr, col[:k].copy(), val[:k].copy()
 
@@ -60,19 +58,14 @@ def advdiff_csr(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[
 def operator(dims: Sequence[int], h: Sequence[float], dt: float, a: Sequence[float], nu: float,
              bc: str | int = "wall", comm: int = PETSC_COMM_SELF, real: bool = False):
     """computeAdvectionDiffusionMatrixCartesianAIJ: dt (a . grad - nu lap) as a stand-in AIJ Mat
-    (no MatShift).  real=True: the real-scalar library's Mat handle (petsc_real.mat_mult,
-    petsc_real.mat_destroy)."""
+    (no MatShift), of the complex library or with real=True of the real-scalar one."""
+    B = _binding(real)
     nx, ny, nz = (int(v) for v in dims)
     b = _BC[bc] if isinstance(bc, str) else int(bc)
     hdl = ctypes.c_void_p()
-    if real:
-        R = _real_lib()
-        R.PetscCall(R.lib().computeAdvectionDiffusionMatrixCartesianAIJ(int(comm), nx, ny, nz, _d3(h), float(dt),
-                                                                        _d3(a), float(nu), b, ctypes.byref(hdl)))
-        return hdl
-    PetscCall(lib().computeAdvectionDiffusionMatrixCartesianAIJ(int(comm), nx, ny, nz, _d3(h), float(dt), _d3(a),
-                                                                float(nu), b, ctypes.byref(hdl)))
-    return Mat(hdl)
+    B.call(B.lib().computeAdvectionDiffusionMatrixCartesianAIJ(int(comm), nx, ny, nz, _d3(h), float(dt), _d3(a),
+                                                               float(nu), b, ctypes.byref(hdl)))
+    return B.Mat(hdl)
 
 
 def config(n: int | Sequence[int] = 32, real: bool = False, **kw) -> AdvDiffConfig:
@@ -81,7 +74,7 @@ def config(n: int | Sequence[int] = 32, real: bool = False, **kw) -> AdvDiffConf
     bc='wall'|'periodic', steps=ntmax, device=True/False, plus any AdvDiffConfig field."""
     cfg = AdvDiffConfig()
     dims = (int(n),) * 3 if np.isscalar(n) else tuple(int(v) for v in n)
-    (_real_lib().lib() if real else lib()).cfp_advdiff_config_default(ctypes.byref(cfg), dims[0])
+    _binding(real).lib().cfp_advdiff_config_default(ctypes.byref(cfg), dims[0])
     cfg.nx, cfg.ny, cfg.nz = dims
     for k, v in kw.items():
         if k == "pc":
@@ -103,15 +96,12 @@ def config(n: int | Sequence[int] = 32, real: bool = False, **kw) -> AdvDiffConf
 
 
 def _run(name: str, cfg: AdvDiffConfig, return_field: bool, real: bool):
+    B = _binding(real)
     res = AdvDiffResult()
     n = int(cfg.nx * cfg.ny * cfg.nz)
-    out = np.empty(n, dtype=np.float64 if real else np.complex128) if return_field else None
+    out = np.empty(n, dtype=B.dtype) if return_field else None
     ptr = out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if out is not None else None
-    if real:
-        R = _real_lib()
-        R.PetscCall(getattr(R.lib(), name)(ctypes.byref(cfg), ctypes.byref(res), ptr))
-    else:
-        PetscCall(getattr(lib(), name)(ctypes.byref(cfg), ctypes.byref(res), ptr))
+    B.call(getattr(B.lib(), name)(ctypes.byref(cfg), ctypes.byref(res), ptr))
     d = res.as_dict()
     if out is not None:  # this rank's rows (all of them on one rank)
         out = out[:d["nlocal"]].copy()
@@ -132,44 +122,16 @@ def run_direct(cfg: AdvDiffConfig, return_field: bool = False, real: bool = Fals
     return _run("AdvectionDiffusionFFTDirect", cfg, return_field, real)
 
 
-def context(ndim: int, dt: float, dims: Sequence[int], a: Sequence[float], nu: float, mins, maxs):
-    """getFFTPrec3DDiffusionContext: the PCSHELL context with the matched numbers
-    lambda_d = a_d dt / h_d, mu_d = nu dt / h_d^2."""
-    from ._lib_ext import FFTPrecDiffusionContext
-    ctx = FFTPrecDiffusionContext()
-    S = PetscScalar.of
-    PetscCall(lib().getFFTPrec3DDiffusionContext(int(ndim), S(dt), int(dims[0]), int(dims[1]), int(dims[2]),
-                                                 S(a[0]), S(a[1]), S(a[2]), S(nu), _d3(mins), _d3(maxs),
-                                                 ctypes.byref(ctx)))
-    return ctx
-
-
 def pc_shell(ctx, upwind: bool = False):
     """A PC of type PCSHELL with the diffusion callbacks registered on ctx (setupFFTPrec3DDiffusion,
-    applyFFT3DPrecDiffusion, destroyFFTPrec3DDiffusion) and set up.  On PETSC_COMM_WORLD of several
-    ranks the FFT matrix is this rank's z slab and ctx.Diag its z-planes of the symbol.
-    upwind=True: setupFFTPrec3DDiffusionUpwind, the operator's symbol for a velocity of either sign."""
-    from .petsc import PC, _fn
-    pc = PC()
-    PetscCall(lib().PCSetType(pc.h, b"shell"))
-    pc.ctx = ctx
-    PetscCall(lib().PCShellSetContext(pc.h, ctypes.addressof(ctx)))
-    PetscCall(lib().PCShellSetSetUp(pc.h, _fn("setupFFTPrec3DDiffusionUpwind" if upwind else "setupFFTPrec3DDiffusion")))
-    PetscCall(lib().PCShellSetApply(pc.h, _fn("applyFFT3DPrecDiffusion")))
-    PetscCall(lib().PCShellSetDestroy(pc.h, _fn("destroyFFTPrec3DDiffusion")))
-    return pc.setup()
+    applyFFT3DPrecDiffusion, destroyFFTPrec3DDiffusion; PC.shell picks them by ctx's type) and set
+    up.  On PETSC_COMM_WORLD of several ranks the FFT matrix is this rank's z slab and ctx.Diag its
+    z-planes of the symbol.  upwind=True: setupFFTPrec3DDiffusionUpwind, the operator's symbol for
+    a velocity of either sign."""
+    return COMPLEX.PC.shell(ctx, upwind).setup()
 
 
-def StructuredContext(n_x, n_y, n_z, a_x, a_y, a_z, nu, dt, delta_x, delta_y, delta_z, FFT_MAT: Mat
-                      ) -> StructuredDiffusionContext:
-    c = StructuredDiffusionContext()
-    c.n_x, c.n_y, c.n_z = int(n_x), int(n_y), int(n_z)
-    for name, v in (("a_x", a_x), ("a_y", a_y), ("a_z", a_z), ("nu", nu), ("dt", dt), ("delta_x", delta_x),
-                    ("delta_y", delta_y), ("delta_z", delta_z)):
-        setattr(c, name, PetscScalar.of(v))
-    c.FFT_MAT = FFT_MAT.h
-    return c
-
-
-def PetscFft3DDiffusionSolver(customCtx: StructuredDiffusionContext, b: Vec, x: Vec) -> None:
-    PetscCall(lib().PetscFft3DDiffusionSolver(customCtx, b.h, x.h))
+# the complex binding's reference-named functions (petsc_real exports the real binding's)
+context = COMPLEX.diffusion_context
+StructuredContext = COMPLEX.structured_diffusion_context
+PetscFft3DDiffusionSolver = COMPLEX.PetscFft3DDiffusionSolver

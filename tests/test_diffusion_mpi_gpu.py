@@ -104,7 +104,7 @@ def _complex_job(job, O):
 def _real_job(O):
     from circulantpreconditioner_amd import petsc_real as R
     L = R.lib()
-    comm = R.Comm().set_world()
+    comm = R.Comm.torch().set_world()
     nx, ny, nz = DIMS
     N = nx * ny * nz
     b = O.c_fill_uniform(N, 47).real.copy()
@@ -114,7 +114,7 @@ def _real_job(O):
     dp = ctypes.c_void_p()
     R.PetscCall(L.MatFFTHIPGetDistPlan(ctx.FFT_MAT, ctypes.byref(dp)))
     out["dist"] = bool(dp.value)
-    diag = R.Vec(ctypes.c_void_p(ctx.Diag))
+    diag = R.Vec.borrow(ctx.Diag)
     out["diag_range"] = diag.ownership_range()
     out["diag"] = diag.array()
     vb, vx = R.Vec.mpi(N, hip=True), R.Vec.mpi(N, hip=True)

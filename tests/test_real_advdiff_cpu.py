@@ -78,12 +78,12 @@ def test_real_library_operator_matmult_on_host_vecs(dif, bc):
     A = dif.operator(dims, h, dt, a, nu, bc, real=True)
     u = np.random.default_rng(2).normal(size=n)
     x, y = R.Vec.seq(n).set_array(u), R.Vec.seq(n)
-    R.mat_mult(A, x, y)
+    A.mult(x, y)
     ref = dense_operator(dims, h, dt, a, nu, bc == "periodic", 0.0) @ u
     assert np.abs(y.array() - ref).max() <= 16 * np.finfo(float).eps * np.abs(ref).max()
     x.destroy()
     y.destroy()
-    R.mat_destroy(A)
+    A.destroy()
 
 
 @pytest.mark.parametrize("bc", ["wall", "periodic"])

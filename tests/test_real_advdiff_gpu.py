@@ -334,7 +334,7 @@ def test_real_diffusion_pcshell(R, oracle, dims):
     err = np.linalg.norm(vx.array() - ref) / np.linalg.norm(ref)
     print(f"real diffusion PCSHELL {dims}: rel L2 vs oracle {err:.3e}")
     assert err < TOL
-    diag = R.Vec(ctypes.c_void_p(ctx.Diag))
+    diag = R.Vec.borrow(ctx.Diag)
     np.testing.assert_allclose(diag.array(), _half(np_diag(dims, *case).reshape(nz, ny, nx), nx), rtol=0, atol=1e-14)
     R.PetscCall(R.lib().VecScale(diag.h, 2.0))  # the caller changes Diag: solve_3D divides by it
     R.PetscCall(R.lib().PCApply(pc, vb.h, vx.h))

@@ -77,7 +77,7 @@ def test_real_pcshell(R, oracle, dims, hip):
     d0 = oracle.c_build_diag_transport(dims, lam)
     ref = _oracle_solve(oracle, dims, lam, b)
     assert np.linalg.norm(vx.array() - ref) / np.linalg.norm(ref) < TOL
-    diag = R.Vec(ctypes.c_void_p(ctx.Diag))
+    diag = R.Vec.borrow(ctx.Diag)
     np.testing.assert_allclose(diag.array(), _half(d0.reshape(nz, ny, nx), nx), rtol=0, atol=1e-14)
     R.PetscCall(R.lib().VecScale(diag.h, 2.0))  # the caller changes Diag: solve_3D divides by it
     R.PetscCall(R.lib().PCApply(pc, vb.h, vx.h))

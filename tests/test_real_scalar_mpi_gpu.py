@@ -43,7 +43,7 @@ def _rank(rank, world, port, dims, lam, q):
         from oracle import oracle as O
         torch.cuda.set_device(0)
         L = R.lib()
-        comm = R.Comm().set_world()
+        comm = R.Comm.torch().set_world()
         nx, ny, nz = dims
         N = nx * ny * nz
         M = nx // 2 + 1
@@ -55,7 +55,7 @@ def _rank(rank, world, port, dims, lam, q):
         dp = ctypes.c_void_p()
         R.PetscCall(L.MatFFTHIPGetDistPlan(ctx.FFT_MAT, ctypes.byref(dp)))
         out["dist"] = bool(dp.value)
-        diag = R.Vec(ctypes.c_void_p(ctx.Diag))
+        diag = R.Vec.borrow(ctx.Diag)
         dlo, dhi = diag.ownership_range()
         out["diag_range"] = (dlo, dhi)
         out["diag"] = diag.array()

@@ -437,7 +437,7 @@ def test_real_pcshell_setups(oracle, kind):
     pc = R.pc_shell(ctx, upwind=True)
     d0 = up_diag(BDIMS, BLAM, mu)
     half = np.ascontiguousarray(d0.reshape(nz, ny, nx)[..., : nx // 2 + 1]).view(np.float64).reshape(-1)
-    diag = R.Vec(ctypes.c_void_p(ctx.Diag))
+    diag = R.Vec.borrow(ctx.Diag)
     assert np.abs(diag.array() - half).max() <= 1e-14 * np.abs(half).max()
     b = oracle.c_fill_uniform(n, 43).real.copy()
     vb, vx = R.Vec.seq(n, hip=True).set_array(b), R.Vec.seq(n, hip=True)
