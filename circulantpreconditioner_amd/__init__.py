@@ -7,6 +7,7 @@ reference's operator interface (``src/FftLinearSolver_3D.h``,
 """
 from ._lib import CirculantError, LIB_PATH, lib  # noqa: F401
 from .plan import (CirculantPlan, RealPlan, advdiff_symbol_1d, advdiff_z_ratio, build_diag_3d,  # noqa: F401
-                   fill_uniform, pointwise_divide, scale, transport_symbol_1d, upwind_to_advdiff, z_route)
+                   fill_uniform, mixed_pass_class, pointwise_divide, scale, transport_symbol_1d, upwind_to_advdiff,
+                   z_route)
 
 __version__ = "0.1.0"

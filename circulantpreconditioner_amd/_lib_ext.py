@@ -219,6 +219,8 @@ def signatures(S) -> list:
             "cfp_advdiff_symbol_1d": ([i64, P(d), P(d), dp], c_int),
             "cfp_advdiff_z_ratio": ([i64, i64, dp, dp, P(d)], c_int),
             "cfp_symbol_z_route": ([i64, i64, i64, dp, dp, c_int, P(c_int), P(d)], c_int),
+            "cfp_mixed_pass_class": ([c_int, i64, c_int, c_int, P(c_int), P(c_int), P(c_int), P(c_int), P(i64),
+                                      P(c_int), P(c_int)], c_int),
         }),
         ("circulant_fft_real.h", BOTH, {
             "cfp_rplan_create": ([P(vp), i64, i64, i64, c_int], c_int),

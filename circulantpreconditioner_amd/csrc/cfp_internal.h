@@ -106,6 +106,17 @@ __host__ __device__ inline cd make_cd(double x, double y) { cd r; r.x = x; r.y =
 // Launchers (cfp_kernels.hip).  tw = forward twiddle table W_n[k] = exp(-2 pi i k / n), k < n.
 hipError_t launch_axis_pass(const PassDesc& p, const cd* in, cd* out, const cd* tw, hipStream_t s);
 bool fast_path_supported(const PassDesc& p);
+// The mixed-radix pass (k_axis_mixed) of an axis of n points and ncols columns, in row mode (the
+// contiguous axis) or column mode, with wave_ncomp = the wave solve's unknowns per cell or 0:
+// columns per block G, LDS column stride L, ping-pong or in-place stages, LDS buffers, twiddles
+// in LDS or global memory, loads in flight U, dynamic LDS bytes and the stage radices.  Host
+// arithmetic only; the error is the one the launch returns for a shape it cannot serve.
+struct MixedClass {
+  int G, L, pingpong, nbuf, tw_lds, U, nst;
+  size_t lds;
+  int fac[24];  // CFP_MR_MAXF
+};
+hipError_t mixed_pass_class(int n, i64 ncols, bool row, int wave_ncomp, MixedClass* c);
 // plane pass: the x and y DFTs of `planes` whole n x n z-planes in one launch (forward, or the
 // conjugated inverse with `scale`); plane_supported(n) lists the built n
 bool plane_supported(i64 n);

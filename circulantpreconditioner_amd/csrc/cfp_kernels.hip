@@ -22,6 +22,7 @@
 // Mixed-radix path (any n <= 4096, incl. primes; the reference's own 10, 100, 10x25x40 ...):
 // LDS-resident Stockham, one specialised radix (8, 4, 2, 3, 5, 7) per stage, butterflies
 // staged in VGPRs so the stages run in place in one LDS buffer.
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -544,18 +545,15 @@ static int factorize(int n, int* fac) {
 }
 
 static const size_t kMixedMaxLds = 160 * 1024 - 2 * 64 * sizeof(i64);  // minus the static base_in/base_out
+static const int kMixedMaxDevices = 64;  // devices whose k_axis_mixed attribute is kept track of
+static_assert(sizeof(MixedClass::fac) / sizeof(int) == CFP_MR_MAXF, "MixedClass::fac holds CFP_MR_MAXF radices");
 
-static hipError_t launch_generic(const PassDesc& p, const cd* in, cd* out, const KArgs& a, hipStream_t s) {
-  if (p.n < 1 || p.n > 4096) return hipErrorNotSupported;
-  const bool row = p.in.pt_stride == 1 && p.out.pt_stride == 1 && p.in.seg_len >= p.n && p.out.seg_len >= p.n;
-  MRArgs g;
-  std::memset(&g, 0, sizeof(g));
-  g.k = a;
-  g.n = p.n;
-  g.ncols = p.ncols;
-  int fac[CFP_MR_MAXF];
-  g.nst = p.n == 1 ? 0 : factorize(p.n, fac);
-  int G = CFP_MR_POINTS / p.n;  // points per block (block-size sweep: DESIGN.md, mixed-radix pass)
+// The geometry of one mixed-radix pass, from (n, ncols, row or column mode, the wave solve's
+// components per cell or 0) alone: what launch_generic launches and cfp_mixed_pass_class reports.
+hipError_t mixed_pass_class(int n, i64 ncols, bool row, int wave_ncomp, MixedClass* c) {
+  if (n < 1 || n > 4096) return hipErrorNotSupported;
+  c->nst = n == 1 ? 0 : factorize(n, c->fac);
+  int G = CFP_MR_POINTS / n;  // points per block (block-size sweep: DESIGN.md, mixed-radix pass)
   if (G < 1) G = 1;
   if (G > 64) G = 64;
   if (!row) {  // power of two for the shift split
@@ -563,17 +561,17 @@ static hipError_t launch_generic(const PassDesc& p, const cd* in, cd* out, const
     while (q * 2 <= G) q *= 2;
     G = q;
   }
-  if ((i64)G > p.ncols) {
-    G = (int)p.ncols;
+  if ((i64)G > ncols) {
+    G = (int)ncols;
     if (!row) {
       int q = 1;
       while (q * 2 <= G) q *= 2;
       G = q;
     }
   }
-  if (p.mode == PASS_FUSED_WAVE) {  // whole cells (ncomp columns) per block
-    const int nc = p.wave.ncomp;
-    if (nc < 2 || nc > 4 || p.ncols % nc != 0) return hipErrorInvalidValue;
+  if (wave_ncomp) {  // whole cells (ncomp columns) per block
+    const int nc = wave_ncomp;
+    if (nc < 2 || nc > 4 || ncols % nc != 0) return hipErrorInvalidValue;
     if (nc == 3) {  // 3 * 2^j columns; the column-mode index split divides by a magic number
       int q = 3;
       while (q * 2 <= G) q *= 2;
@@ -583,10 +581,41 @@ static hipError_t launch_generic(const PassDesc& p, const cd* in, cd* out, const
       G &= ~(nc - 1);
     }
   }
+  c->G = G;
+  c->L = row ? n : n + 1;
+  c->pingpong = 0;
+  for (int i = 0; i < c->nst; ++i)
+    if (c->fac[i] > 8) c->pingpong = 1;
+  if (G * n > CFP_MR_MAXPTS) c->pingpong = 1;
+  c->nbuf = (c->pingpong || wave_ncomp) ? 2 : 1;
+  size_t lds = (size_t)c->nbuf * G * c->L * sizeof(cd);
+  c->tw_lds = lds + (size_t)n * sizeof(cd) <= 96 * 1024 ? 1 : 0;
+  if (c->tw_lds) lds += (size_t)n * sizeof(cd);
+  c->lds = lds;
+  const int pts = G * n;
+  c->U = pts <= 2 * CFP_MR_THREADS ? 2 : (pts <= 4 * CFP_MR_THREADS ? 4 : 8);
+  if (lds > kMixedMaxLds) return hipErrorInvalidConfiguration;
+  return hipSuccess;
+}
+
+static hipError_t launch_generic(const PassDesc& p, const cd* in, cd* out, const KArgs& a, hipStream_t s) {
+  const bool row = p.in.pt_stride == 1 && p.out.pt_stride == 1 && p.in.seg_len >= p.n && p.out.seg_len >= p.n;
+  MixedClass c;
+  const int wave_nc = p.mode != PASS_FUSED_WAVE ? 0 : (p.wave.ncomp ? p.wave.ncomp : -1);  // 0 components: refused
+  const hipError_t ce = mixed_pass_class(p.n, p.ncols, row, wave_nc, &c);
+  if (ce != hipSuccess) return ce;
+  MRArgs g;
+  std::memset(&g, 0, sizeof(g));
+  g.k = a;
+  g.n = p.n;
+  g.ncols = p.ncols;
+  g.nst = c.nst;
+  const int* fac = c.fac;
+  const int G = c.G;
   g.G = G;
   g.gshift = is_pow2(G) ? ilog2(G) : -1;
   g.G_M = mr_magic((uint32_t)G);
-  g.L = row ? p.n : p.n + 1;
+  g.L = c.L;
   int ns = 1;
   for (int i = 0; i < g.nst; ++i) {
     MRStage& S = g.st[i];
@@ -601,30 +630,27 @@ static hipError_t launch_generic(const PassDesc& p, const cd* in, cd* out, const
   g.n_M = mr_magic((uint32_t)p.n);
   g.segin_M = mr_magic((uint32_t)(p.in.seg_len > 0 ? p.in.seg_len : 1));
   g.segout_M = mr_magic((uint32_t)(p.out.seg_len > 0 ? p.out.seg_len : 1));
-  g.pingpong = 0;
-  for (int i = 0; i < g.nst; ++i)
-    if (fac[i] > 8) g.pingpong = 1;
-  if (G * p.n > CFP_MR_MAXPTS) g.pingpong = 1;
-  g.nbuf = (g.pingpong || p.mode == PASS_FUSED_WAVE) ? 2 : 1;
-  size_t lds = (size_t)g.nbuf * G * g.L * sizeof(cd);
-  g.tw_lds = lds + (size_t)p.n * sizeof(cd) <= 96 * 1024 ? 1 : 0;
-  if (g.tw_lds) lds += (size_t)p.n * sizeof(cd);
-  if (lds > kMixedMaxLds) return hipErrorInvalidConfiguration;
-  static bool attr_set = false;
-  if (!attr_set) {
+  g.pingpong = c.pingpong;
+  g.nbuf = c.nbuf;
+  g.tw_lds = c.tw_lds;
+  const size_t lds = c.lds;
+  // the attribute belongs to the function object of the current device: once per device
+  static std::atomic<bool> attr_set[kMixedMaxDevices];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMixedMaxDevices) return hipErrorInvalidDevice;
+  if (!attr_set[dev].load(std::memory_order_acquire)) {
     const void* kf[] = {(const void*)k_axis_mixed<true, 2>, (const void*)k_axis_mixed<true, 4>,
                         (const void*)k_axis_mixed<true, 8>, (const void*)k_axis_mixed<false, 2>,
                         (const void*)k_axis_mixed<false, 4>, (const void*)k_axis_mixed<false, 8>};
     for (const void* f : kf) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMixedMaxLds);
     (void)hipGetLastError();  // a refused attribute must not surface as this launch's error
-    attr_set = true;
+    attr_set[dev].store(true, std::memory_order_release);
   }
   const i64 blocks = (p.ncols + G - 1) / G;
-  const int pts = G * p.n;
   const dim3 gr((unsigned)blocks), bl(CFP_MR_THREADS);
 #define CFP_MR_LAUNCH(ROWV)                                                                          \
-  if (pts <= 2 * CFP_MR_THREADS) hipLaunchKernelGGL((k_axis_mixed<ROWV, 2>), gr, bl, lds, s, in, out, g, p.mode); \
-  else if (pts <= 4 * CFP_MR_THREADS) hipLaunchKernelGGL((k_axis_mixed<ROWV, 4>), gr, bl, lds, s, in, out, g, p.mode); \
+  if (c.U == 2) hipLaunchKernelGGL((k_axis_mixed<ROWV, 2>), gr, bl, lds, s, in, out, g, p.mode); \
+  else if (c.U == 4) hipLaunchKernelGGL((k_axis_mixed<ROWV, 4>), gr, bl, lds, s, in, out, g, p.mode); \
   else hipLaunchKernelGGL((k_axis_mixed<ROWV, 8>), gr, bl, lds, s, in, out, g, p.mode);
   if (row) { CFP_MR_LAUNCH(true) } else { CFP_MR_LAUNCH(false) }
 #undef CFP_MR_LAUNCH

@@ -1274,6 +1274,26 @@ extern "C" int cfp_build_diag_3d(double* diag, const double* cx, const double* c
   return e == hipSuccess ? CFP_SUCCESS : hip_error(e, "build diag");
 }
 
+extern "C" int cfp_mixed_pass_class(int n, int64_t ncols, int row, int wave_ncomp, int* G, int* pingpong, int* tw_lds,
+                                    int* U, int64_t* lds_bytes, int* nstages, int radices[24]) {
+  if (!G || !pingpong || !tw_lds || !U || !lds_bytes || !nstages || !radices)
+    return set_error(CFP_ERR_ARG_NULL, "NULL argument");
+  if (ncols < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "ncols must be >= 1");
+  if (wave_ncomp < 0) return set_error(CFP_ERR_ARG_OUTOFRANGE, "wave_ncomp must be 0 (no wave solve) or 2..4");
+  MixedClass c;
+  std::memset(&c, 0, sizeof(c));
+  const hipError_t e = mixed_pass_class(n, (i64)ncols, row != 0, wave_ncomp, &c);
+  if (e != hipSuccess) return hip_error(e, "mixed-radix pass");
+  *G = c.G;
+  *pingpong = c.pingpong;
+  *tw_lds = c.tw_lds;
+  *U = c.U;
+  *lds_bytes = (int64_t)c.lds;
+  *nstages = c.nst;
+  for (int i = 0; i < 24; ++i) radices[i] = i < c.nst ? c.fac[i] : 0;
+  return CFP_SUCCESS;
+}
+
 extern "C" int cfp_transport_symbol_1d(int64_t n, double* out) {
   if (!out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
   if (n < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "n must be >= 1");

@@ -387,6 +387,20 @@ def z_route(dims: Sequence, lam: Sequence, mu: Sequence = (0, 0, 0), upwind: boo
     return {1: "zrec", 2: "zrec2", 3: "zrecb"}.get(k.value, "fft"), (float(r[0]), float(r[1]))
 
 
+def mixed_pass_class(n: int, ncols: int, row: bool, wave_ncomp: int = 0) -> dict:
+    """The geometry of the LDS mixed-radix pass over an axis of n points and ncols columns, in row
+    mode (the contiguous axis) or column mode, with the wave block solve's unknowns per cell or 0
+    (cfp_mixed_pass_class: the launch's own arithmetic; no GPU needed): {"G", "pingpong", "tw_lds",
+    "U", "lds_bytes", "radices"}.  Raises CirculantError for a shape the launch would refuse."""
+    G, pp, tw, U, nst = (ctypes.c_int() for _ in range(5))
+    lds, rad = ctypes.c_int64(), (ctypes.c_int * 24)()
+    check(lib().cfp_mixed_pass_class(int(n), int(ncols), int(bool(row)), int(wave_ncomp), ctypes.byref(G),
+                                     ctypes.byref(pp), ctypes.byref(tw), ctypes.byref(U), ctypes.byref(lds),
+                                     ctypes.byref(nst), rad))
+    return {"G": G.value, "pingpong": bool(pp.value), "tw_lds": bool(tw.value), "U": U.value,
+            "lds_bytes": lds.value, "radices": list(rad[:nst.value])}
+
+
 def pointwise_divide(w: torch.Tensor, x: torch.Tensor, y: torch.Tensor, stream=None) -> torch.Tensor:
     n = w.numel()
     check(lib().cfp_pointwise_divide(_dev_ptr(w, n, "w"), _dev_ptr(x, n, "x"), _dev_ptr(y, n, "y"), n,

@@ -268,6 +268,16 @@ int cfp_advdiff_z_ratio(int64_t nx, int64_t ny, const double lam[6], const doubl
  * of the (mapped) pair otherwise.  Any grid but 256^3 gives CFP_MID_KERNEL_FFT. */
 int cfp_symbol_z_route(int64_t nx, int64_t ny, int64_t nz, const double lam[6], const double mu[6], int upwind,
                        int *kind, double ratios_host[2]);
+/* host (no GPU needed): the geometry of the LDS mixed-radix pass that serves an axis of n points
+ * (1..4096) and ncols columns -- row != 0 for the contiguous axis, wave_ncomp = the wave block
+ * solve's unknowns per cell (2..4) or 0 -- computed by the arithmetic the launch itself uses:
+ * columns per workgroup G, ping-pong (1) or in-place (0) stages, the twiddle table in LDS (1) or
+ * read from global memory (0), loads in flight per thread U (2, 4 or 8), dynamic LDS bytes, and
+ * the stage radices in order (nstages of them; the rest of the 24 entries are 0; a radix above 8
+ * is a direct-sum prime stage).  A shape the launch would refuse returns the launch's error
+ * (CFP_ERR_LIB). */
+int cfp_mixed_pass_class(int n, int64_t ncols, int row, int wave_ncomp, int *G, int *pingpong, int *tw_lds,
+                         int *U, int64_t *lds_bytes, int *nstages, int radices[24]);
 
 #ifdef __cplusplus
 }

@@ -100,3 +100,28 @@ def test_real_plan_errors(cp):
         plan.set_transport_symbol((1.0, 1.0, 1.0))
         with pytest.raises(ValueError):
             plan.apply(torch.zeros(511, dtype=torch.float64, device="cuda"))
+
+
+# the row kernels k_rx<M> (r2c and c2r) with a partial last tile of rows at both extremes -- 3 or 5
+# rows, and one row more than a tile (RCfg<M>::T) -- which also puts odd and prime-factored y
+# lengths (65, 33, 17, 9) on the y passes of the half-spectrum and Nyquist sub-plans
+ROW_TILES = {16: 64, 32: 64, 64: 32, 128: 16, 256: 8, 512: 8}  # M = nx / 2 -> rows per workgroup
+
+
+@pytest.mark.parametrize("n", [g for M, T in ROW_TILES.items() for g in ((2 * M, 3, 1), (2 * M, 1, 5), (2 * M, T + 1, 1))],
+                         ids=lambda n: "x".join(map(str, n)))
+def test_real_plan_partial_row_tiles_vs_oracle(cp, oracle, n):
+    assert (n[1] * n[2]) % ROW_TILES[n[0] // 2] != 0
+    N = int(np.prod(n))
+    lam = (0.6, 0.15, 0.02)
+    b = np.random.default_rng(7 + N).standard_normal(N)
+    ref = oracle.c_solve_3d(oracle.c_build_diag_transport(n, lam), b.astype(np.complex128), n)
+    assert np.abs(ref.imag).max() <= 1e-12 * np.abs(ref).max()
+    with cp.RealPlan(n) as plan:
+        plan.set_transport_symbol(lam)
+        x = plan.apply(torch.from_numpy(b).cuda()).cpu().numpy()
+        assert np.linalg.norm(x - ref.real) <= TOL * np.linalg.norm(ref.real)
+        assert np.abs(x - ref.real).max() <= TOL * np.abs(ref.real).max()
+        t = torch.from_numpy(b).cuda()
+        plan.apply(t, out=t)  # in place
+        assert np.array_equal(t.cpu().numpy(), x)

@@ -469,3 +469,39 @@ def test_wave_gmres_fused_dots_equal_unfused():
     assert rf["fused_dots"] == rf["total_its"] and rf["fused_norms"] == rf["steps"]
     assert ru["fused_dots"] == 0 and ru["fused_norms"] == 0
     assert np.linalg.norm(Uf - Uu) <= 1e-11 * np.linalg.norm(Uu)
+
+
+# The fused wave pass on the LDS mixed-radix kernel's other classes (test_mixed_class_cpu.py checks
+# the same table without a GPU): a direct-sum prime stage (ping-pong) on the fused axis and on the
+# plain ones, and blocks above 2,048 points (ping-pong by size, twiddles in global memory, up to
+# 128 KB of LDS).  (dim, dims, class of the fused pass, its columns per block)
+WAVE_MIXED = [(3, (6, 5, 22), "pingpong_prime", 64), (3, (22, 6, 5), "inplace", 64), (3, (5, 22, 6), "inplace", 64),
+              (3, (4, 13, 3), "inplace", 64), (3, (2, 1, 1000), "pingpong_size", 4),
+              (2, (10, 33), "pingpong_prime", 12), (2, (33, 10), "refused", 48), (2, (3, 1000), "pingpong_size", 3),
+              (1, (143,), "pingpong_prime", 2), (1, (1001,), "pingpong_prime", 2)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dim,dims,cls,G", WAVE_MIXED,
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_wave_plan_mixed_pass_classes_match_oracle(dim, dims, cls, G):
+    import torch
+    from circulantpreconditioner_amd import mixed_pass_class
+    from mixed_cases import in_class
+    d3 = tuple(dims) + (1,) * (3 - len(dims))
+    fused = max(a for a in range(3) if d3[a] > 1)  # the wave plan fuses its last axis longer than 1
+    n, ncomp = d3[fused], dim + 1
+    c = mixed_pass_class(n, ncomp * int(np.prod(d3)) // n, False, ncomp)  # interleaved components: column mode
+    assert in_class(cls, n, c) and c["G"] == G and G % ncomp == 0, c
+    kappa = (0.079, 0.05, 0.11 if dim == 3 else 0.0)
+    m = ncomp * int(np.prod(dims))
+    b = _rand(m, 21)
+    xo = OW.block_solve(dims, kappa, b, dim=dim)
+    plan = W.WavePlan(dims, dim=dim).set_symbol(kappa)
+    x = plan.apply(torch.from_numpy(b).cuda())
+    assert np.linalg.norm(x.cpu().numpy() - xo) <= 1e-12 * np.linalg.norm(xo)
+    t = torch.from_numpy(b).cuda()
+    plan.apply(t, out=t)  # in place
+    assert np.linalg.norm(t.cpu().numpy() - xo) <= 1e-12 * np.linalg.norm(xo)
+    assert torch.equal(t, x)
+    plan.close()
