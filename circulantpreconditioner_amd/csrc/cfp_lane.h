@@ -1,5 +1,5 @@
 // cfp_lane.h -- cross-lane moves of complex values inside a wave64 (gfx950), used by the lane
-// DFTs of the 3-sweep kernels (cfp_three_pass.hip, cfp_wave_three.hip).  DPP moves run on the
+// DFTs of the 3-sweep kernels (cfp_three_pass.hip, cfp_tp_*.hip, cfp_wave_three.hip).  DPP moves run on the
 // VALU; lane ^ 16 has no DPP form on gfx9 and takes ds_swizzle (LDS pipe, no LDS memory).
 #pragma once
 #include "cfp_fft_device.h"

@@ -29,7 +29,7 @@ std::vector<cd> transport_product(const std::vector<cd>& hat, std::complex<doubl
 
 // max over (kx, ky) of |lamz / (1 + sx[kx] + sy[ky] + lamz)|, s_d = lambda_d (1 - e^{-2 pi i k / n_d}):
 // the ratio a of the z recurrence u_z = a u_{z-1} + w_z that the transport symbol's z part is
-// (cfp_three_pass.hip k_tp_mid_rec).  A zero denominator gives infinity.
+// (cfp_tp_rec.hip k_tp_mid_rec).  A zero denominator gives infinity.
 double transport_z_ratio(const std::vector<cd>& sx, const std::vector<cd>& sy, std::complex<double> lz) {
   double amax = 0.0;
   const double lzn = std::abs(lz);
@@ -93,7 +93,7 @@ void upwind_to_advdiff(int nc, const double* lam, const double* mu, double* lam_
 // Along z the advection-diffusion symbol of a column, d - p e^{-i theta} - q e^{i theta} with
 // p = lamz + muz, q = muz, d = 1 + sx[kx] + sy[ky] + p + q, factors as
 // beta (1 - a e^{-i theta}) (1 - b e^{i theta}), beta the root of beta^2 - d beta + p q = 0 of
-// larger modulus, a = p / beta, b = q / beta (cfp_three_pass.hip k_tp_mid_rec2).  ratios = max |a|,
+// larger modulus, a = p / beta, b = q / beta (cfp_tp_rec.hip k_tp_mid_rec2).  ratios = max |a|,
 // max |b| over the columns; beta = 0 gives infinity.
 std::complex<double> advdiff_z_beta(cd x, cd y, std::complex<double> p, std::complex<double> q) {
   const std::complex<double> d = std::complex<double>(x.x + y.x + 1.0, x.y + y.y) + p + q;

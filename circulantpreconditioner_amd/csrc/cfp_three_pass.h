@@ -1,11 +1,12 @@
-// cfp_three_pass.h -- the 3-sweep apply for 128^3 and 256^3 grids (cfp_three_pass.hip).
+// cfp_three_pass.h -- the 3-sweep apply for 128^3 and 256^3 grids (the schedule and the row sweeps:
+// cfp_three_pass.hip; the dispatch: cfp_tp_dispatch.hip; the other kernel families: cfp_tp_*.hip).
 #pragma once
 #include "cfp_internal.h"
 
 namespace cfp {
 
 // Row sweeps (P1 / P3 of the scalar and wave 3-sweeps) with units in XCD order
-// (r05j-r05l, cfp_three_pass.hip kRowsXCD; the real-data rows keep blockIdx order).
+// (r05j-r05l, cfp_tp_launch.h kRowsXCD; the real-data rows keep blockIdx order).
 // -DCFP_ROWS_XCD=0 builds the blockIdx order for A/B.
 #ifndef CFP_ROWS_XCD
 #define CFP_ROWS_XCD 1

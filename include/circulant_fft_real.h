@@ -14,7 +14,7 @@
  * 1 x ny x nz grid), z fused with the symbol, inverse y, then c2r along x with the 1/N scale.
  * Requires nx even with nx/2 in {16, 32, ..., 512} and ny * nz > 1.
  *
- * At 256^3 the default is a 3-sweep schedule (cfp_three_pass.hip): r2c rows + the 32-point y1
+ * At 256^3 the default is a 3-sweep schedule (cfp_tp_rows_r2c.hip, cfp_tp_mid.hip): r2c rows + the 32-point y1
  * DFT of a four-step y split | y2 + z + divide + inverse on the half spectrum | y1 inverse + c2r
  * rows, ~32 N bytes per apply.
  *

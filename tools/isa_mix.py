@@ -2,7 +2,7 @@
 """Static instruction mix of gfx950 kernels (CPU only): compiles a .hip source for the device,
 disassembles it, and counts the instructions of every kernel whose symbol contains a pattern.
 
-  python tools/isa_mix.py circulantpreconditioner_amd/csrc/cfp_three_pass.hip k_tp_mid_sw
+  python tools/isa_mix.py circulantpreconditioner_amd/csrc/cfp_tp_mid.hip k_tp_mid_sw
 
 Per kernel: total, f64 VALU, other VALU, cross-lane moves (DPP, permlane), LDS, global memory
 and scalar instructions.  The counts are of the code, not of its execution (loops count once).

@@ -14,12 +14,9 @@
 //   which 10: blocks of 8 x, memory alone; 11: blocks of 8 x, full kernel
 //   which 12: blocks of 2 x, memory alone; 13: blocks of 2 x, full kernel
 #define CFP_KEXP 1
-#include "cfp_three_pass.hip"
+#include "cfp_tp_mid.hip"  // k_tp_mid
 namespace cfp {
 thread_local LaunchStamp g_stamp;  // defined in cfp_plan.hip in the library
-hipError_t launch_three_pass_sq(int, int, const cd*, cd*, const TPArgs&, TPShape, hipStream_t) {
-  return hipErrorNotSupported;
-}
 }  // namespace cfp
 
 using namespace cfp;

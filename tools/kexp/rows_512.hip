@@ -13,12 +13,9 @@
 //   21-26: the same six with the next unit's LDS-DMA prefetch (k_tp_rows<.., NPF = kRowsNPF>)
 //   34-37: the prefetching product with NPF = 4 .. 7 slots
 #define CFP_KEXP 1
-#include "cfp_three_pass.hip"
+#include "cfp_three_pass.hip"  // k_tp_rows, kRowsNPF
 namespace cfp {
 thread_local LaunchStamp g_stamp;  // defined in cfp_plan.hip in the library
-hipError_t launch_three_pass_sq(int, int, const cd*, cd*, const TPArgs&, TPShape, hipStream_t) {
-  return hipErrorNotSupported;
-}
 }  // namespace cfp
 
 using namespace cfp;

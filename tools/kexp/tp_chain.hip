@@ -9,13 +9,10 @@
 //   + 4096: P2 loads non-temporally (its input is read once)
 //   + 256 * w: P2 = k_tp_mid_w8 (8 waves, 32 points per thread), w = 1: no register prefetch, 2: 8 slots, 3: 16
 #define CFP_KEXP 1
-#include "cfp_three_pass.hip"
+#include "cfp_three_pass.hip"  // k_tp_rows
+#include "cfp_tp_mid.hip"      // k_tp_mid_sw, dif_pairs
 namespace cfp {
 thread_local LaunchStamp g_stamp;  // defined in cfp_plan.hip in the library
-// launch_three_pass routes 100^3 to cfp_three_pass_sq.hip, which this harness does not build
-hipError_t launch_three_pass_sq(int, int, const cd*, cd*, const TPArgs&, TPShape, hipStream_t) {
-  return hipErrorNotSupported;
-}
 }  // namespace cfp
 
 namespace cfp {

@@ -2,19 +2,16 @@
 // Built with CFP_KEXP, which is the only build that may instantiate k_tp_mid_sw with PROBE != 0
 // (a probe drops part of the work, so its output is invalid).  Each launch runs P2 in place on
 // the whole grid with the product's persistent grid (one 1024-thread workgroup per CU).
-//   which < 64:  k_tp_mid_sw<64, 8, 256, which>   (PR_* bits of cfp_three_pass.hip)
+//   which < 64:  k_tp_mid_sw<64, 8, 256, which>   (PR_* bits of cfp_tp_device.h)
 //   which = 100: k_tp_mid<0, 64, 8, 256> (the DPP lane-DFT kernel)
 //   which = 200 + P: k_tp_mid_rec<P> (the recurrence kernel; P = PR_NO_Y2 | PR_NO_ZMATH (no scan)
 //                | PR_NO_LOAD | PR_NO_STORE), lambda_z = 0.02
 //   which += 1000: one workgroup per unit instead of the persistent grid
 #define CFP_KEXP 1
-#include "cfp_three_pass.hip"
+#include "cfp_tp_mid.hip"  // k_tp_mid_sw, k_tp_mid
+#include "cfp_tp_rec.hip"  // k_tp_mid_rec
 namespace cfp {
 thread_local LaunchStamp g_stamp;  // defined in cfp_plan.hip in the library
-// launch_three_pass routes 100^3 to cfp_three_pass_sq.hip, which this harness does not build
-hipError_t launch_three_pass_sq(int, int, const cd*, cd*, const TPArgs&, TPShape, hipStream_t) {
-  return hipErrorNotSupported;
-}
 }  // namespace cfp
 
 using namespace cfp;

@@ -33,7 +33,7 @@ def load(d, counter):
 
 
 def pass_name(kname: str):
-    # the 3-sweep schedule's kernels (cfp_three_pass.hip): rows fwd / mid fused / rows inv
+    # the 3-sweep schedule's kernels (cfp_three_pass.hip, cfp_tp_mid.hip): rows fwd / mid fused / rows inv
     t = re.search(r"k_tp_rows<(true|false)", kname)
     if t:
         return "pass2_xy_rows_inv" if t.group(1) == "true" else "pass0_xy_rows_fwd"

@@ -15,7 +15,7 @@ import re
 import sqlite3
 
 # --bench: the complex 3-sweep kernels of bench.py's legs, each with its own grid edge
-# (template arguments as cfp_three_pass.hip instantiates them; real-data and wave kernels
+# (template arguments as cfp_three_pass.hip and cfp_tp_mid.hip instantiate them; real-data and wave kernels
 # move a different byte count per grid and are left blank).
 BENCH_GRIDS = [
     (r"k_tp_mid_sw<64, 8, 256, 0, true, 256,", 256),
