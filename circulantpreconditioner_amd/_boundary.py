@@ -42,6 +42,8 @@ _SHELL = {
     ("FFTPrecDiffusionContext", True): ("setupFFTPrec3DDiffusionUpwind", "applyFFT3DPrecDiffusion",
                                         "destroyFFTPrec3DDiffusion"),
     ("FFTPrecWaveContext", False): ("setupFFTPrec3DWave", "applyFFT3DPrecWave", "destroyFFTPrec3DWave"),
+    ("FFTPrecWaveRealContext", False): ("setupFFTPrec3DWaveRealData", "applyFFT3DPrecWaveRealData",
+                                        "destroyFFTPrec3DWaveRealData"),
 }
 
 
@@ -465,7 +467,7 @@ class PC(_Object):
     def set_shell(self, ctx, upwind: bool = False) -> "PC":
         """PCSetType(pc, PCSHELL); PCShellSetContext; PCShellSetSetUp/Apply/Destroy with the
         callbacks of ctx's kind (the registration the reference never does, ToDo.md:1): a
-        transport, diffusion or wave context.  upwind=True: the setup with the upwind symbol, for
+        transport, diffusion, wave or real-data wave context.  upwind=True: the setup with the upwind symbol, for
         numbers of either sign (setupFFTPrec3DUpwind / setupFFTPrec3DDiffusionUpwind)."""
         names = _SHELL.get((type(ctx).__name__, bool(upwind)))
         if names is None:

@@ -168,6 +168,12 @@ class FFTPrecWaveContext(ctypes.Structure):
                 ("c0", ctypes.c_double), ("plan", ctypes.c_void_p), ("dim", ctypes.c_int64)]
 
 
+class FFTPrecWaveRealContext(ctypes.Structure):
+    """struct FFTPrecWaveRealContext (include/wave_system_real.h): FFTPrecWaveContext's members and
+    order, `plan` a cfp_wave_rplan_t; the same struct in both scalar builds (no PetscScalar member)."""
+    _fields_ = list(FFTPrecWaveContext._fields_)
+
+
 def signatures(S) -> list:
     """The signature table: [(group, build, {name: (argtypes, restype)})].  S is PetscScalar (by
     value a 16-byte struct) or c_double; a group is the header that declares its functions, and
@@ -489,6 +495,20 @@ def signatures(S) -> list:
             "cfp_wave_config_default": ([P(WaveConfig), i64], None),
             "cfp_wave_config_default_dim": ([P(WaveConfig), i64, c_int], None),
             "WaveSystemGMRES": ([P(WaveConfig), P(WaveResult), P(d)], c_int),
+        }),
+        # the real-data wave plan and its PCSHELL
+        ("wave_system_real.h", BOTH, {
+            "cfp_wave_rplan_supported": ([i64, i64, i64, c_int], c_int),
+            "cfp_wave_rplan_create": ([P(vp), i64, i64, i64, c_int, c_int], c_int),
+            "cfp_wave_rplan_destroy": ([vp], c_int),
+            "cfp_wave_rplan_set_symbol": ([vp, P(d), d], c_int),
+            "cfp_wave_rplan_apply": ([vp, dp, dp, vp], c_int),
+            "cfp_wave_rplan_apply_strided": ([vp, dp, dp, c_int, vp], c_int),
+            "cfp_wave_rplan_num_passes": ([vp, P(c_int)], c_int),
+            "cfp_wave_rplan_time_passes": ([vp, dp, dp, c_int, c_int, P(d), vp], c_int),
+            "setupFFTPrec3DWaveRealData": ([vp], c_int),
+            "applyFFT3DPrecWaveRealData": ([vp, vp, vp], c_int),
+            "destroyFFTPrec3DWaveRealData": ([vp], c_int),
         }),
     ]
 

@@ -16,7 +16,7 @@ from __future__ import annotations
 from ._boundary import (ADD_VALUES, COMPLEX as B, INSERT_VALUES, KSP_REASONS, MATOP_MULT, NORM_1,  # noqa: F401
                         NORM_2, NORM_INFINITY, PC_LEFT, PC_RIGHT, PETSC_COMM_SELF, PETSC_COMM_WORLD, PETSC_DEFAULT,
                         PetscError)
-from ._lib_ext import FFTPrecWaveContext, PetscScalar  # noqa: F401
+from ._lib_ext import FFTPrecWaveContext, FFTPrecWaveRealContext, PetscScalar  # noqa: F401
 
 lib, PetscCall, fn, set_comm_world, _S = B.lib, B.call, B.fn, B.set_comm_world, B.S
 Vec, Comm, Mat, PC, KSP = B.Vec, B.Comm, B.Mat, B.PC, B.KSP

@@ -21,7 +21,7 @@ from ._boundary import (ADD_VALUES, INSERT_VALUES, KSP_REASONS, MATOP_MULT, NORM
                         NORM_INFINITY, PC_LEFT, PC_RIGHT, PETSC_COMM_SELF, PETSC_COMM_WORLD, PETSC_DEFAULT,
                         REAL as B, PetscError)
 from ._lib import REAL_LIB_PATH as LIB_PATH  # noqa: F401
-from ._lib_ext import AdvDiffConfig, AdvDiffResult, AIJInfo  # noqa: F401
+from ._lib_ext import AdvDiffConfig, AdvDiffResult, AIJInfo, FFTPrecWaveRealContext  # noqa: F401
 
 # the names of petsc.py, bound to this library
 lib, PetscCall, fn, set_comm_world = B.lib, B.call, B.fn, B.set_comm_world

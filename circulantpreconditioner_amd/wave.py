@@ -5,6 +5,9 @@ SURVEY.md §8f row f2, BASELINE config 4).
 unknowns per cell (pressure, dim momentum components; idx = cell*(dim+1) + comp as the
 reference's Un, tests/WaveSystem_SphericalExplosion_impl_seq.cxx:19,57-68), one HIP plan,
 at most 5 HBM sweeps.  dim = 3 by default; the reference mains' own default is 2-D (50 x 50).
+``RealWavePlan``: the same inverse on real data (include/wave_system_real.h): r2c rows, the
+half spectrum through the complex plan's y and fused passes, c2r rows; float64 tensors, or the
+real parts of complex128 ones.
 ``wave_csr``: the reference operator (src/WaveSystem.cxx:92-176) on a Cartesian grid.
 ``config``/``run``: WaveSystem_impl_seq's time loop with the block-circulant PCSHELL.
 """
@@ -112,6 +115,81 @@ class WavePlan:
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
             lib().cfp_wave_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def real_plan_supported(dims: Sequence[int], dim: int = 3) -> bool:
+    """cfp_wave_rplan_supported: whether RealWavePlan serves the grid (host arithmetic, no device)."""
+    nx, ny, nz = _dims3(dims)
+    return bool(lib().cfp_wave_rplan_supported(nx, ny, nz, int(dim)))
+
+
+class RealWavePlan:
+    """x = S^{-1} b for real b on an nx*ny*nz grid with dim + 1 interleaved components, on the half
+    spectrum kx <= nx/2: dim = 3, or dim = 2 with nz = 1; nx/2 a power of two in [16, 512]
+    (``real_plan_supported``; anything else raises).  Half the memory traffic of ``WavePlan``'s
+    five passes."""
+
+    def __init__(self, dims: Sequence[int], device: int | None = None, dim: int = 3):
+        nx, ny, nz = _dims3(dims)
+        self.dims = (nx, ny, nz)
+        self.dim = int(dim)
+        self.ncomp = self.dim + 1
+        self.size = self.ncomp * nx * ny * nz
+        self._h = None
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        h = ctypes.c_void_p()
+        check(lib().cfp_wave_rplan_create(ctypes.byref(h), nx, ny, nz, self.dim, self.device))
+        self._h = h
+
+    def set_symbol(self, kappa: Sequence[float], c0: float = C0) -> "RealWavePlan":
+        check(lib().cfp_wave_rplan_set_symbol(self._h, _d3(kappa), float(c0)))
+        return self
+
+    def _ptr(self, t: torch.Tensor, name: str) -> int:
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float64, torch.complex128):
+            raise TypeError(f"{name} must be a float64 or complex128 torch.Tensor")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{name} must be a device tensor on cuda:{self.device}")
+        if not t.is_contiguous() or t.numel() != self.size:
+            raise ValueError(f"{name} must be contiguous with {self.size} elements")
+        return t.data_ptr()
+
+    def apply(self, b: torch.Tensor, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """float64 b: x = S^{-1} b as float64.  complex128 b: the same on its real parts (the
+        imaginary parts are ignored), returned as complex128 with a zero imaginary part.  out may
+        be b."""
+        if out is None:
+            out = torch.empty_like(b)
+        if out.dtype != b.dtype:
+            raise TypeError("out must have b's dtype")
+        es = 2 if b.dtype == torch.complex128 else 1
+        check(lib().cfp_wave_rplan_apply_strided(self._h, self._ptr(b, "b"), self._ptr(out, "out"), es,
+                                                 _stream_handle(stream)))
+        return out
+
+    def num_passes(self) -> int:
+        n = ctypes.c_int()
+        check(lib().cfp_wave_rplan_num_passes(self._h, ctypes.byref(n)))
+        return n.value
+
+    def time_passes(self, b: torch.Tensor, x: torch.Tensor, iters: int = 10, stream=None) -> list:
+        """Mean device ms of each launch of the schedule (events between them)."""
+        ms = (ctypes.c_double * self.num_passes())()
+        es = 2 if b.dtype == torch.complex128 else 1
+        check(lib().cfp_wave_rplan_time_passes(self._h, self._ptr(b, "b"), self._ptr(x, "x"), es, int(iters), ms,
+                                               _stream_handle(stream)))
+        return list(ms)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().cfp_wave_rplan_destroy(self._h)
             self._h = None
 
     def __del__(self):
