@@ -24,7 +24,6 @@
 
 #include <complex>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <vector>
 
@@ -37,11 +36,6 @@
 
 using namespace cfp;
 
-#define HIPCHK(expr)                                        \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return cfp::hip_error(_e, #expr); \
-  } while (0)
 #define NCCLCHK(expr)                                                                            \
   do {                                                                                           \
     ncclResult_t _r = (expr);                                                                    \
@@ -314,7 +308,7 @@ bool slab_rec2_auto(int P) { return slab_rec2_ranks(P); }
 struct SlabRank {
   SlabLayout L;
   int device = 0;
-  std::map<int, cd*> tw;
+  TwiddleCache tw;
   cd* colsym = nullptr;
   cd* colsym3 = nullptr;  // 3-sweep schedule: the global [kx + nx ky] table
   cd* axsym = nullptr;
@@ -347,15 +341,6 @@ struct SlabRank {
   }
   int pieces() const { return pieces_req ? pieces_req : auto_pieces(L); }
   bool three() const { return !steps.empty() && steps[0].kind == K_TP; }
-  int ensure_tw(int n) {
-    if (tw.count(n)) return CFP_SUCCESS;
-    std::vector<cd> h = host_twiddles(n, -1);
-    cd* d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(cd) * h.size()));
-    HIPCHK(hipMemcpy(d, h.data(), sizeof(cd) * h.size(), hipMemcpyHostToDevice));
-    tw[n] = d;
-    return CFP_SUCCESS;
-  }
   int ensure_work2() {
     if (!work2) {
       HIPCHK(hipMalloc(&work2, sizeof(cd) * (size_t)L.work));
@@ -369,12 +354,10 @@ struct SlabRank {
     const int K = pieces();
     steps = slab_steps(L, sched, K, L_APPLY_SEP);
     diag_steps = slab_steps(L, sched, K, L_APPLY_DIAG);
+    cd* t = nullptr;  // (uploads only)
     for (const auto* list : {&steps, &diag_steps})
       for (const Step& s : *list)
-        if (s.kind == K_PASS || s.kind == K_TP) {
-          int rc = ensure_tw(s.pass.n);
-          if (rc) return rc;
-        }
+        if (s.kind == K_PASS || s.kind == K_TP) CFPCHK(tw.get(s.pass.n, &t));
     return sym ? refill() : CFP_SUCCESS;  // the new schedule's symbol tables
   }
   int refill() { return set_advdiff(lam_, mu_); }
@@ -390,7 +373,6 @@ struct SlabRank {
     zrec2_tab = nullptr;
   }
   void release() {
-    for (auto& kv : tw) hipFree(kv.second);
     tw.clear();
     if (colsym) hipFree(colsym);
     if (colsym3) hipFree(colsym3);

@@ -59,6 +59,7 @@ __device__ __forceinline__ cd cmul(cd a, cd b) {
   return make_cd(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
 }
 __device__ __forceinline__ cd cconj(cd a) { return make_cd(a.x, -a.y); }
+__device__ __forceinline__ cd shfl_cd(cd v, int lane) { return make_cd(__shfl(v.x, lane), __shfl(v.y, lane)); }
 // a / b = (a * conj(b)) / |b|^2, the complex VecPointwiseDivide of the reference
 // (src/FftLinearSolver_3D.c:174).  A zero divisor gives 0, as PETSc's VecPointwiseDivide does
 // (third-party semantics, PETSc src/vec/vec/impls/seq/bvec2.c): a singular symbol's null modes

@@ -10,6 +10,8 @@
 // The closed-form symbols' arithmetic and the rule that picks the 256^3 middle kernel are
 // cfp_symbol.cpp's (decide_z_route); the plan stores the decision (z_route) and plan_z_route()
 // is the one place that says what the next apply launches.
+// Also defines cfp_host.h's toolkit shared by every plan flavour: error plumbing, check_device,
+// twiddles and TwiddleCache, the natural pass geometry, wave_field_pass and the pass timer.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -48,12 +50,6 @@ int hip_error(hipError_t e, const char* what) {
 }
 }  // namespace cfp
 
-#define HIPCHK(expr)                                     \
-  do {                                                   \
-    hipError_t _e = (expr);                              \
-    if (_e != hipSuccess) return cfp::hip_error(_e, #expr); \
-  } while (0)
-
 extern "C" const char* cfp_last_error(void) { return g_err.c_str(); }
 extern "C" const char* cfp_version(void) { return "circulant_fft 0.1.0 (gfx950)"; }
 
@@ -74,8 +70,15 @@ extern "C" int cfp_device_copy(void* dst, const void* src, size_t bytes, void* s
   return CFP_SUCCESS;
 }
 
-// ------------------------------------------------------------------ twiddles
+// ------------------------------------------------------------------ shared host toolkit (cfp_host.h)
 namespace cfp {
+
+int check_device(int device) {
+  int ndev = 0;
+  HIPCHK(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return set_error(CFP_ERR_ARG_OUTOFRANGE, "device %d out of range", device);
+  return CFP_SUCCESS;
+}
 
 std::vector<cd> host_twiddles(int n, int sign) {
   std::vector<cd> t((size_t)n);
@@ -84,6 +87,27 @@ std::vector<cd> host_twiddles(int n, int sign) {
     t[k] = make_cd((double)cosl(a), (double)(sign * sinl(a)));
   }
   return t;
+}
+
+int TwiddleCache::get(int n, cd** out) {
+  auto it = tab.find(n);
+  if (it == tab.end()) {
+    const std::vector<cd> h = host_twiddles(n, -1);
+    cd* d = nullptr;
+    HIPCHK(hipMalloc(&d, sizeof(cd) * (size_t)n));
+    hipError_t e = hipMemcpy(d, h.data(), sizeof(cd) * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      hipFree(d);
+      return hip_error(e, "twiddle upload");
+    }
+    it = tab.emplace(n, d).first;
+  }
+  *out = it->second;
+  return CFP_SUCCESS;
+}
+void TwiddleCache::clear() {
+  for (auto& kv : tab) hipFree(kv.second);
+  tab.clear();
 }
 
 int ilog2_exact(i64 v) {
@@ -113,6 +137,53 @@ void natural_cols(int axis, const i64 n[3], i64* ncols, i64* inner_n) {
   *inner_n = axis == 0 ? 1 : (axis == 1 ? n[0] : n[0] * n[1]);
 }
 
+PassDesc wave_field_pass(int ncomp, i64 g0, i64 n1, i64 n2, const double2* const tab[3], double c0, int fused,
+                         int axis, int mode, double scale) {
+  const i64 g[3] = {g0, n1, n2}, m[3] = {ncomp * g0, n1, n2};
+  PassDesc d;
+  d.n = (int)g[axis];
+  d.in = d.out = natural_side(axis, m);
+  natural_cols(axis, m, &d.ncols, &d.inner_n);
+  d.mode = mode;
+  d.scale = scale;
+  d.colsym = d.axsym = d.diag = nullptr;
+  for (int a = 0; a < 3; ++a) {
+    d.wave.tab[a] = tab[a];
+    d.wave.n[a] = g[a];
+  }
+  d.wave.c0sq = c0 * c0;
+  d.wave.fused = fused;
+  d.wave.ncomp = ncomp;
+  return d;
+}
+
+int time_passes(size_t np, bool paired, int iters, const std::function<int(std::vector<hipEvent_t>*)>& run,
+                double* ms_out) {
+  if (iters < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "iters must be >= 1");
+  std::vector<double> acc(np, 0.0);
+  std::vector<hipEvent_t> ev(paired ? 2 * np : np + 1);
+  for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+  int rc = CFP_SUCCESS;
+  for (int it = 0; it < iters && rc == CFP_SUCCESS; ++it) {
+    rc = run(&ev);
+    if (rc) break;
+    hipError_t e = hipEventSynchronize(ev.back());
+    if (e != hipSuccess) {
+      rc = hip_error(e, "event sync");
+      break;
+    }
+    for (size_t i = 0; i < np; ++i) {
+      float ms = 0.f;
+      hipEventElapsedTime(&ms, ev[paired ? 2 * i : i], ev[paired ? 2 * i + 1 : i + 1]);
+      acc[i] += ms;
+    }
+  }
+  for (auto& e : ev) hipEventDestroy(e);
+  if (rc) return rc;
+  for (size_t i = 0; i < np; ++i) ms_out[i] = acc[i] / iters;
+  return CFP_SUCCESS;
+}
+
 }  // namespace cfp
 
 // ------------------------------------------------------------------ plan
@@ -120,7 +191,7 @@ struct cfp_plan_s {
   int device = 0;
   i64 n[3] = {1, 1, 1};
   i64 N = 1;
-  std::map<int, cd*> tw;  // device forward twiddles per axis length
+  TwiddleCache tw;        // device forward twiddles per axis length
   int sym_kind = 0;       // 0 none, 1 separable, 2 explicit diag
   uint64_t sym_version = 0;  // bumped by every symbol setter (cfp_plan_symbol_version)
   cd* colsym = nullptr;   // separable: per column of the fused axis (sum over the other axes)
@@ -181,16 +252,6 @@ thread_local ApplyStamp g_apply_stamp;
 extern "C" void cfp_apply_stamp_clear(void) { cfp::g_apply_stamp.start = cfp::g_apply_stamp.stop = nullptr; }
 
 namespace {
-
-int ensure_tw(cfp_plan_s* p, int n) {
-  if (p->tw.count(n)) return CFP_SUCCESS;
-  std::vector<cd> h = host_twiddles(n, -1);
-  cd* d = nullptr;
-  HIPCHK(hipMalloc(&d, sizeof(cd) * (size_t)n));
-  HIPCHK(hipMemcpy(d, h.data(), sizeof(cd) * (size_t)n, hipMemcpyHostToDevice));
-  p->tw[n] = d;
-  return CFP_SUCCESS;
-}
 
 struct Step {
   int axis;
@@ -414,10 +475,10 @@ int run_apply(cfp_plan_s* p, const cd* diag_override, const cd* b, cd* x, hipStr
     const Step& q = st[i];
     if (q.tp >= 0) {
       const int tn = (int)p->n[0];
-      int trc = ensure_tw(p, tn);
-      if (trc) return trc;
       TPArgs a;
-      a.tw = p->tw[tn];
+      cd* ttw = nullptr;
+      CFPCHK(p->tw.get(tn, &ttw));
+      a.tw = ttw;
       a.colsym = p->colsym;
       a.axsym = p->axsym;
       a.scale = q.scale ? invN : 1.0;
@@ -480,10 +541,10 @@ int run_apply(cfp_plan_s* p, const cd* diag_override, const cd* b, cd* x, hipStr
     }
     if (q.sub == 4) {
       const int pn = (int)p->n[0];
-      int prc = ensure_tw(p, pn);
-      if (prc) return prc;
+      cd* ptw = nullptr;
+      CFPCHK(p->tw.get(pn, &ptw));
       if (ev) HIPCHK(hipEventRecord((*ev)[2 * i], s));
-      hipError_t e = launch_plane_pass(q.mode == PASS_PLANE_INV, pn, p->n[2], q.from_b ? b : x, x, p->tw[pn],
+      hipError_t e = launch_plane_pass(q.mode == PASS_PLANE_INV, pn, p->n[2], q.from_b ? b : x, x, ptw,
                                        q.scale ? invN : 1.0, s);
       if (e != hipSuccess) return hip_error(e, "plane pass launch");
       if (ev) HIPCHK(hipEventRecord((*ev)[2 * i + 1], s));
@@ -500,10 +561,10 @@ int run_apply(cfp_plan_s* p, const cd* diag_override, const cd* b, cd* x, hipStr
     i64 off = 0;
     PassDesc d = make_pass(p, q, step_mode(p, q, diag_override != nullptr), q.scale ? invN : 1.0, &off);
     if (diag_override) d.diag = diag_override;
-    int rc = ensure_tw(p, d.n);
-    if (rc) return rc;
+    cd* tw = nullptr;
+    CFPCHK(p->tw.get(d.n, &tw));
     if (ev) HIPCHK(hipEventRecord((*ev)[2 * i], s));
-    hipError_t e = launch_axis_pass(d, (q.from_b ? b : x) + off, x + off, p->tw[d.n], s);
+    hipError_t e = launch_axis_pass(d, (q.from_b ? b : x) + off, x + off, tw, s);
     if (e != hipSuccess) return hip_error(e, "axis pass launch");
     if (ev) HIPCHK(hipEventRecord((*ev)[2 * i + 1], s));
   }
@@ -523,9 +584,9 @@ int run_transform(cfp_plan_s* p, bool inverse, const cd* in, cd* out, hipStream_
     i64 off = 0;
     PassDesc d = make_pass(p, Step{ax, inverse ? PASS_INV : PASS_FWD, first, false, 0, -1},
                            inverse ? PASS_INV : PASS_FWD, 1.0, &off);
-    int rc = ensure_tw(p, d.n);
-    if (rc) return rc;
-    hipError_t e = launch_axis_pass(d, first ? in : out, out, p->tw[d.n], s);
+    cd* tw = nullptr;
+    CFPCHK(p->tw.get(d.n, &tw));
+    hipError_t e = launch_axis_pass(d, first ? in : out, out, tw, s);
     if (e != hipSuccess) return hip_error(e, "axis pass launch");
     first = false;
   }
@@ -675,9 +736,7 @@ extern "C" int cfp_plan_create(cfp_plan_t* plan, int64_t nx, int64_t ny, int64_t
     split[a][0] = (int)best;
     split[a][1] = (int)(dims_in[a] / best);
   }
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return set_error(CFP_ERR_ARG_OUTOFRANGE, "device %d out of range", device);
+  CFPCHK(check_device(device));
   DeviceGuard dg(device);
   std::unique_ptr<cfp_plan_s> p(new cfp_plan_s);
   p->device = device;
@@ -685,11 +744,11 @@ extern "C" int cfp_plan_create(cfp_plan_t* plan, int64_t nx, int64_t ny, int64_t
   p->N = nx * ny * nz;
   std::memcpy(p->split, split, sizeof(split));
   order_axes(p.get());
+  cd* tw = nullptr;  // (uploads only)
   for (int a : p->axes) {
     if (p->split[a][0]) {
-      int rc = ensure_tw(p.get(), p->split[a][0]);
-      if (!rc) rc = ensure_tw(p.get(), p->split[a][1]);
-      if (rc) return rc;
+      CFPCHK(p->tw.get(p->split[a][0], &tw));
+      CFPCHK(p->tw.get(p->split[a][1], &tw));
       // four-step twiddles W_n^j (j < 4096) and W_n^{4096 i} (i <= n / 4096), long double
       const i64 n = p->n[a];
       const i64 nhi = n / 4096 + 1;
@@ -709,13 +768,9 @@ extern "C" int cfp_plan_create(cfp_plan_t* plan, int64_t nx, int64_t ny, int64_t
       HIPCHK(hipMemcpy(p->tw4hi[a], hi.data(), sizeof(cd) * (size_t)nhi, hipMemcpyHostToDevice));
       continue;
     }
-    int rc = ensure_tw(p.get(), (int)p->n[a]);
-    if (rc) return rc;
+    CFPCHK(p->tw.get((int)p->n[a], &tw));
   }
-  if (p->axes.empty()) {
-    int rc = ensure_tw(p.get(), 1);
-    if (rc) return rc;
-  }
+  if (p->axes.empty()) CFPCHK(p->tw.get(1, &tw));
   *plan = p.release();
   return CFP_SUCCESS;
 }
@@ -724,7 +779,7 @@ extern "C" int cfp_plan_destroy(cfp_plan_t p) {
   if (!p) return CFP_SUCCESS;
   DeviceGuard dg(p->device);
   free_symbol(p);
-  for (auto& kv : p->tw) hipFree(kv.second);
+  p->tw.clear();
   for (int a = 0; a < 3; ++a) {
     if (p->tw4lo[a]) hipFree(p->tw4lo[a]);
     if (p->tw4hi[a]) hipFree(p->tw4hi[a]);
@@ -1221,29 +1276,10 @@ extern "C" int cfp_plan_pass_info(cfp_plan_t p, int pass, int* axis, int* n, int
 
 extern "C" int cfp_plan_time_passes(cfp_plan_t p, const double* b, double* x, int iters, double* ms_out, void* stream) {
   if (!p || !b || !x || !ms_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  if (iters < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "iters must be >= 1");
   DeviceGuard dg(p->device);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t np = apply_steps(p).size();
-  std::vector<double> acc(np, 0.0);
-  std::vector<hipEvent_t> ev(2 * np);
-  for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  int rc = CFP_SUCCESS;
-  for (int it = 0; it < iters && rc == CFP_SUCCESS; ++it) {
-    rc = run_apply(p, nullptr, (const cd*)b, (cd*)x, s, &ev);
-    if (rc) break;
-    hipError_t e = hipEventSynchronize(ev[2 * np - 1]);
-    if (e != hipSuccess) { rc = hip_error(e, "event sync"); break; }
-    for (size_t i = 0; i < np; ++i) {
-      float ms = 0.f;
-      hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]);
-      acc[i] += ms;
-    }
-  }
-  for (auto& e : ev) hipEventDestroy(e);
-  if (rc) return rc;
-  for (size_t i = 0; i < np; ++i) ms_out[i] = acc[i] / iters;
-  return CFP_SUCCESS;
+  return time_passes(apply_steps(p).size(), true, iters, [&](std::vector<hipEvent_t>* ev) {
+    return run_apply(p, nullptr, (const cd*)b, (cd*)x, (hipStream_t)stream, ev);
+  }, ms_out);
 }
 
 // ------------------------------------------------------------------ vector kernels

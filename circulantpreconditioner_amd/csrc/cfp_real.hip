@@ -25,8 +25,6 @@
 
 namespace cfp {
 
-__device__ __forceinline__ cd shfl_cd(cd v, int lane) { return make_cd(__shfl(v.x, lane), __shfl(v.y, lane)); }
-
 // M = nx/2 points per row FFT, PTS points per thread, first radix R0, T rows per workgroup
 template <int M, int PTS, int R0, int T, bool INV>
 __global__ void __launch_bounds__(T*(M / PTS)) k_rx(const double* in_r, cd* half, cd* nyq, double* out_r,
@@ -127,17 +125,6 @@ static hipError_t launch_rx(int M, bool inv, const double* in, cd* half, cd* nyq
 
 using namespace cfp;
 
-#define HIPCHK(expr)                                        \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return cfp::hip_error(_e, #expr); \
-  } while (0)
-#define CFPCHK(expr)              \
-  do {                            \
-    int _r = (expr);              \
-    if (_r != CFP_SUCCESS) return _r; \
-  } while (0)
-
 struct cfp_rplan_s {
   int device = 0;
   i64 n[3] = {1, 1, 1};
@@ -146,7 +133,8 @@ struct cfp_rplan_s {
   cfp_plan_t nyq = nullptr;   // 1 x ny x nz Nyquist column kx = nx/2
   cd* H = nullptr;
   cd* Q = nullptr;
-  cd* twn = nullptr;  // W_nx
+  TwiddleCache tw;
+  cd* twn = nullptr;  // tw's W_nx
   bool has_sym = false;
   // the Nyquist grid's passes overlap the half-spectrum passes (5-pass schedule only; created on
   // first use: a process holding an extra stream ran the 128^3 apply on the default stream 9 %
@@ -188,7 +176,7 @@ void free_rplan(cfp_rplan_s* p) {
   if (p->nyq) cfp_plan_destroy(p->nyq);
   if (p->H) hipFree(p->H);
   if (p->Q) hipFree(p->Q);
-  if (p->twn) hipFree(p->twn);
+  p->tw.clear();
   if (p->colsym3) hipFree(p->colsym3);
   if (p->colsymq) hipFree(p->colsymq);
   if (p->axsym3) hipFree(p->axsym3);
@@ -303,14 +291,12 @@ extern "C" int cfp_rplan_create(cfp_rplan_t* plan, int64_t nx, int64_t ny, int64
     return rc;
   }
   DeviceGuard g(device);
-  std::vector<cd> tw = host_twiddles((int)nx, -1);
   hipError_t e = hipMalloc(&p->H, sizeof(cd) * (size_t)(M * ny * nz));
   if (e == hipSuccess) e = hipMalloc(&p->Q, sizeof(cd) * (size_t)(ny * nz));
-  if (e == hipSuccess) e = hipMalloc(&p->twn, sizeof(cd) * (size_t)nx);
-  if (e == hipSuccess) e = hipMemcpy(p->twn, tw.data(), sizeof(cd) * (size_t)nx, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
+  rc = e == hipSuccess ? p->tw.get((int)nx, &p->twn) : hip_error(e, "real plan buffers");
+  if (rc != CFP_SUCCESS) {
     free_rplan(p);
-    return hip_error(e, "real plan buffers");
+    return rc;
   }
   *plan = p;
   return CFP_SUCCESS;
@@ -431,30 +417,10 @@ extern "C" int cfp_rplan_num_passes(cfp_rplan_t p, int* passes) {
 extern "C" int cfp_rplan_time_passes(cfp_rplan_t p, const double* b, double* x, int iters, double* ms_out,
                                      void* stream) {
   if (!p || !b || !x || !ms_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  if (iters < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "iters must be >= 1");
   DeviceGuard g(p->device);
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<hipEvent_t> ev(5);
-  for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  double acc[4] = {0, 0, 0, 0};
-  int rc = CFP_SUCCESS;
-  for (int it = 0; it < iters && rc == CFP_SUCCESS; ++it) {
-    rc = run_real(p, b, x, s, &ev);
-    if (rc) break;
-    if (hipEventSynchronize(ev[4]) != hipSuccess) {
-      rc = set_error(CFP_ERR_LIB, "event sync");
-      break;
-    }
-    for (int i = 0; i < 4; ++i) {
-      float ms = 0.f;
-      hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-      acc[i] += ms;
-    }
-  }
-  for (auto& e : ev) hipEventDestroy(e);
-  if (rc) return rc;
-  for (int i = 0; i < 4; ++i) ms_out[i] = acc[i] / iters;
-  return CFP_SUCCESS;
+  return time_passes(4, false, iters, [&](std::vector<hipEvent_t>* ev) {
+    return run_real(p, b, x, (hipStream_t)stream, ev);
+  }, ms_out);
 }
 
 // ------------------------------------------------------------------ real <-> complex layouts

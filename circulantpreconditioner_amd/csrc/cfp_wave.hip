@@ -16,8 +16,6 @@
 // per-frequency block symbol (cfp_fft_device.h: wave_solve).
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <map>
 #include <memory>
 #include <vector>
 
@@ -27,14 +25,9 @@
 #include "cfp_host.h"
 #include "cfp_internal.h"
 #include "cfp_three_pass.h"
+#include "cfp_wave_host.h"
 
 using namespace cfp;
-
-#define HIPCHK(expr)                                        \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return cfp::hip_error(_e, #expr); \
-  } while (0)
 
 struct cfp_wave_plan_s {
   int device = 0;
@@ -42,7 +35,7 @@ struct cfp_wave_plan_s {
   i64 N = 1;  // cells
   int dim = 3;
   int ncomp = 4;  // dim + 1 unknowns per cell
-  std::map<int, cd*> tw;
+  TwiddleCache tw;
   double2* tab[3] = {nullptr, nullptr, nullptr};
   bool has_sym = false;
   double c0 = 0.0;
@@ -54,20 +47,10 @@ struct cfp_wave_plan_s {
 
 namespace {
 
-int ensure_tw(cfp_wave_plan_s* p, int n) {
-  if (p->tw.count(n)) return CFP_SUCCESS;
-  std::vector<cd> h = host_twiddles(n, -1);
-  cd* d = nullptr;
-  HIPCHK(hipMalloc(&d, sizeof(cd) * (size_t)n));
-  HIPCHK(hipMemcpy(d, h.data(), sizeof(cd) * (size_t)n, hipMemcpyHostToDevice));
-  p->tw[n] = d;
-  return CFP_SUCCESS;
-}
-
-// the pass over `axis` of the interleaved 4-component field
+// the pass over `axis` of the interleaved field: y, z and fused by wave_field_pass; along x the
+// columns (comp, y, z) have point stride ncomp
 PassDesc wave_pass(const cfp_wave_plan_s* p, int axis, int mode, double scale) {
-  PassDesc d;
-  d.n = (int)p->n[axis];
+  PassDesc d = wave_field_pass(p->ncomp, p->n[0], p->n[1], p->n[2], p->tab, p->c0, p->fused, axis, mode, scale);
   if (axis == 0) {
     Side s;
     s.inner_stride = 1;
@@ -79,28 +62,14 @@ PassDesc wave_pass(const cfp_wave_plan_s* p, int axis, int mode, double scale) {
     d.in = d.out = s;
     d.inner_n = p->ncomp;
     d.ncols = p->ncomp * p->n[1] * p->n[2];
-  } else {
-    const i64 m[3] = {p->ncomp * p->n[0], p->n[1], p->n[2]};
-    d.in = d.out = natural_side(axis, m);
-    natural_cols(axis, m, &d.ncols, &d.inner_n);
   }
-  d.mode = mode;
-  d.scale = scale;
-  d.colsym = d.axsym = d.diag = nullptr;
-  for (int a = 0; a < 3; ++a) {
-    d.wave.tab[a] = p->tab[a];
-    d.wave.n[a] = p->n[a];
-  }
-  d.wave.c0sq = p->c0 * p->c0;
-  d.wave.fused = p->fused;
-  d.wave.ncomp = p->ncomp;
   return d;
 }
 
 int launch(cfp_wave_plan_s* p, const PassDesc& d, const cd* in, cd* out, hipStream_t s) {
-  int rc = ensure_tw(p, d.n);
-  if (rc) return rc;
-  hipError_t e = launch_axis_pass(d, in, out, p->tw[d.n], s);
+  cd* tw = nullptr;
+  CFPCHK(p->tw.get(d.n, &tw));
+  hipError_t e = launch_axis_pass(d, in, out, tw, s);
   return e == hipSuccess ? CFP_SUCCESS : hip_error(e, "wave axis pass");
 }
 
@@ -141,7 +110,7 @@ int run_wave(cfp_wave_plan_s* p, const cd* b, cd* x, hipStream_t s, std::vector<
     if (ev) HIPCHK(hipEventRecord((*ev)[i], s));
     if (q.tp >= 0) {
       WTPArgs a;
-      a.tw = p->tw[128];
+      a.tw = p->tw.at(128);
       a.wave = wave_pass(p, 2, PASS_FUSED_WAVE, 1.0).wave;
       a.wave.fused = 2;
       a.scale = q.scale ? invN : 1.0;
@@ -198,9 +167,7 @@ extern "C" int cfp_wave_plan_create_dim(cfp_wave_plan_t* plan, int64_t nx, int64
     return set_error(CFP_ERR_ARG_SIZ, "a %d-D wave system has n = 1 along the axes above its dimension", dim);
   if (nx > 1024 || ny > 1024 || nz > 1024)
     return set_error(CFP_ERR_SUP, "wave plan: axis lengths above 1024 are not supported");
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return set_error(CFP_ERR_ARG_OUTOFRANGE, "device %d out of range", device);
+  CFPCHK(check_device(device));
   DeviceGuard g(device);
   std::unique_ptr<cfp_wave_plan_s> p(new cfp_wave_plan_s);
   p->device = device;
@@ -213,10 +180,8 @@ extern "C" int cfp_wave_plan_create_dim(cfp_wave_plan_t* plan, int64_t nx, int64
   for (int a = 0; a < 3; ++a)
     if (p->n[a] > 1) p->axes.push_back(a);
   p->fused = p->axes.empty() ? 0 : p->axes.back();
-  for (int a = 0; a < 3; ++a) {
-    int rc = ensure_tw(p.get(), (int)p->n[a]);
-    if (rc) return rc;
-  }
+  cd* tw = nullptr;  // (uploads only)
+  for (int a = 0; a < 3; ++a) CFPCHK(p->tw.get((int)p->n[a], &tw));
   *plan = p.release();
   return CFP_SUCCESS;
 }
@@ -228,7 +193,7 @@ extern "C" int cfp_wave_plan_create(cfp_wave_plan_t* plan, int64_t nx, int64_t n
 extern "C" int cfp_wave_plan_destroy(cfp_wave_plan_t p) {
   if (!p) return CFP_SUCCESS;
   DeviceGuard g(p->device);
-  for (auto& kv : p->tw) hipFree(kv.second);
+  p->tw.clear();
   for (int a = 0; a < 3; ++a)
     if (p->tab[a]) hipFree(p->tab[a]);
   if (p->post_partial) hipFree(p->post_partial);
@@ -236,23 +201,15 @@ extern "C" int cfp_wave_plan_destroy(cfp_wave_plan_t p) {
   return CFP_SUCCESS;
 }
 
-// p_d[k] = kappa_d c0 (1 - cos theta), q_d[k] = kappa_d sin theta, theta = 2 pi k / n_d
+// the per-axis (p, q) tables (cfp_wave_host.h: axis_table, q = (double)sinl(theta) everywhere)
 extern "C" int cfp_wave_plan_set_symbol(cfp_wave_plan_t p, const double kappa[3], double c0) {
   if (!p || !kappa) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  if (!(c0 > 0.0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "c0 must be > 0");
-  for (int a = 0; a < 3; ++a)
-    if (!(kappa[a] >= 0.0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "kappa must be >= 0");
+  if (const char* why = wave::symbol_refusal(kappa, c0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "%s", why);
   DeviceGuard g(p->device);
   for (int a = 0; a < 3; ++a) {
-    const i64 n = p->n[a];
-    std::vector<double2> t((size_t)n);
-    for (i64 k = 0; k < n; ++k) {
-      const long double th = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
-      t[(size_t)k] = make_double2((double)((long double)kappa[a] * c0 * (1.0L - cosl(th))),
-                                  (double)((long double)kappa[a] * sinl(th)));
-    }
-    if (!p->tab[a]) HIPCHK(hipMalloc(&p->tab[a], sizeof(double2) * (size_t)n));
-    HIPCHK(hipMemcpy(p->tab[a], t.data(), sizeof(double2) * (size_t)n, hipMemcpyHostToDevice));
+    const std::vector<double> t = wave::axis_table(p->n[a], p->n[a], kappa[a], c0, false);
+    if (!p->tab[a]) HIPCHK(hipMalloc(&p->tab[a], sizeof(double) * t.size()));
+    HIPCHK(hipMemcpy(p->tab[a], t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
   }
   p->c0 = c0;
   p->has_sym = true;
@@ -335,30 +292,8 @@ extern "C" int cfp_wave_plan_num_passes(cfp_wave_plan_t p, int* passes) {
 extern "C" int cfp_wave_plan_time_passes(cfp_wave_plan_t p, const double* b, double* x, int iters, double* ms_out,
                                          void* stream) {
   if (!p || !b || !x || !ms_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  if (iters < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "iters must be >= 1");
   DeviceGuard g(p->device);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t np = wave_steps(p).size();
-  std::vector<double> acc(np, 0.0);
-  std::vector<hipEvent_t> ev(np + 1);
-  for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  int rc = CFP_SUCCESS;
-  for (int it = 0; it < iters && rc == CFP_SUCCESS; ++it) {
-    rc = run_wave(p, (const cd*)b, (cd*)x, s, &ev);
-    if (rc) break;
-    hipError_t e = hipEventSynchronize(ev[np]);
-    if (e != hipSuccess) {
-      rc = hip_error(e, "event sync");
-      break;
-    }
-    for (size_t i = 0; i < np; ++i) {
-      float ms = 0.f;
-      hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-      acc[i] += ms;
-    }
-  }
-  for (auto& e : ev) hipEventDestroy(e);
-  if (rc) return rc;
-  for (size_t i = 0; i < np; ++i) ms_out[i] = acc[i] / iters;
-  return CFP_SUCCESS;
+  return time_passes(wave_steps(p).size(), false, iters, [&](std::vector<hipEvent_t>* ev) {
+    return run_wave(p, (const cd*)b, (cd*)x, (hipStream_t)stream, ev);
+  }, ms_out);
 }

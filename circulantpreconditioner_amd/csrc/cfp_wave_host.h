@@ -1,12 +1,42 @@
-// cfp_wave_real_host.h -- the host arithmetic of the real-data wave plan (cfp_wave_real.hip):
-// which grids it serves, its schedule and its symbol tables.  Plain C++ without a HIP include,
-// so a stand-alone program can run it under a host sanitizer (tools/wave_real_host_check.cpp).
+// cfp_wave_host.h -- the host arithmetic of the wave family: the symbol's validation and per-axis
+// tables shared by the complex wave plan (cfp_wave.hip), its slab-backed PCSHELL (wave_system.cpp)
+// and the real-data wave plan (cfp_wave_real.hip), and which grids the real-data plan serves and
+// its schedule.  Plain C++ without a HIP include, so a stand-alone program can run it under a
+// host sanitizer (tools/wave_real_host_check.cpp).
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
 namespace cfp {
+namespace wave {
+
+// NULL when (kappa, c0) is a wave symbol, else why not
+inline const char* symbol_refusal(const double kappa[3], double c0) {
+  if (!(c0 > 0.0)) return "c0 must be > 0";
+  for (int a = 0; a < 3; ++a)
+    if (!(kappa[a] >= 0.0)) return "kappa must be >= 0";
+  return nullptr;
+}
+
+// (p, q)[k] = (kappa c0 (1 - cos theta), kappa sin theta), theta = 2 pi k / n, interleaved, for
+// k < count.  exact_self_mirror: q = 0 exactly at the self-mirrored frequencies k = 0 and 2 k = n,
+// where sin theta is 0 but (double)sinl(pi) is not.  The real-data plan sets it: its Nyquist field
+// (kx = nx / 2) is a real-data field of its own only with q = 0 there.  The complex plan and the
+// slab PCSHELL leave it off and keep (double)sinl(theta) everywhere, the tables their recorded
+// results were measured with.
+inline std::vector<double> axis_table(int64_t n, int64_t count, double kappa, double c0, bool exact_self_mirror) {
+  std::vector<double> t((size_t)(2 * count));
+  for (int64_t k = 0; k < count; ++k) {
+    const long double th = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
+    t[(size_t)(2 * k)] = (double)((long double)kappa * c0 * (1.0L - cosl(th)));
+    const bool self_mirrored = k == 0 || 2 * k == n;
+    t[(size_t)(2 * k + 1)] = exact_self_mirror && self_mirrored ? 0.0 : (double)((long double)kappa * sinl(th));
+  }
+  return t;
+}
+
+}  // namespace wave
 namespace wave_real {
 
 constexpr int64_t kMaxAxis = 4096;   // y / z passes: the mixed-radix pass's longest axis
@@ -53,20 +83,11 @@ inline std::vector<Step> schedule(int64_t ny, int64_t nz) {
   return st;
 }
 
-// (p, q)[k] = (kappa c0 (1 - cos theta), kappa sin theta), theta = 2 pi k / n, interleaved, for
-// k < count (cfp_wave_plan_set_symbol's arithmetic).  The self-mirrored frequencies k = 0 and
-// 2 k = n get q = 0 exactly: there sin theta is 0, and the Nyquist field relies on it.
-inline std::vector<double> axis_table(int64_t n, int64_t count, double kappa, double c0) {
-  std::vector<double> t((size_t)(2 * count));
-  for (int64_t k = 0; k < count; ++k) {
-    const long double th = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
-    t[(size_t)(2 * k)] = (double)((long double)kappa * c0 * (1.0L - cosl(th)));
-    t[(size_t)(2 * k + 1)] = (k == 0 || 2 * k == n) ? 0.0 : (double)((long double)kappa * sinl(th));
-  }
-  return t;
+// the x table of the half spectrum and the Nyquist column: k = 0 .. nx/2, nx/2 + 1 entries (the
+// plan's tables have the self-mirrored q exactly 0)
+inline std::vector<double> x_table(int64_t nx, double kappa, double c0) {
+  return wave::axis_table(nx, nx / 2 + 1, kappa, c0, true);
 }
-// the x table of the half spectrum and the Nyquist column: k = 0 .. nx/2, nx/2 + 1 entries
-inline std::vector<double> x_table(int64_t nx, double kappa, double c0) { return axis_table(nx, nx / 2 + 1, kappa, c0); }
 
 }  // namespace wave_real
 }  // namespace cfp

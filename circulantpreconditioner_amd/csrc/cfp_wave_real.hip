@@ -18,19 +18,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <map>
 #include <vector>
 
 #include "../../include/circulant_fft.h"
 #include "../../include/wave_system_real.h"
 #include "cfp_fft_device.h"
 #include "cfp_host.h"
-#include "cfp_wave_real_host.h"
+#include "cfp_wave_host.h"
 
 namespace cfp {
 namespace {
-
-__device__ __forceinline__ cd wr_shfl(cd v, int lane) { return make_cd(__shfl(v.x, lane), __shfl(v.y, lane)); }
 
 // k_rx's FFT shapes per M (TPC = M / PTS divides 64) and R = cell-rows per workgroup
 template <int M> struct WRCfg;
@@ -104,7 +101,7 @@ __global__ void __launch_bounds__(WRCfg<M>::R* C*(M / WRCfg<M>::PTS))
 #pragma unroll
     for (int t = 0; t < PTS; ++t) {
       const int k = tpc + t * TPC;
-      const cd za = wr_shfl(v[(PTS - t) % PTS], pl), zb = wr_shfl(v[PTS - 1 - t], pl);
+      const cd za = shfl_cd(v[(PTS - t) % PTS], pl), zb = shfl_cd(v[PTS - 1 - t], pl);
       const cd zm = tpc == 0 ? za : zb;  // Z[M - k]
       const cd e = make_cd(0.5 * (v[t].x + zm.x), 0.5 * (v[t].y - zm.y));
       const cd d = make_cd(v[t].x - zm.x, v[t].y + zm.y);  // Z[k] - conj Z[M-k]
@@ -139,7 +136,7 @@ __global__ void __launch_bounds__(WRCfg<M>::R* C*(M / WRCfg<M>::PTS))
 #pragma unroll
     for (int t = 0; t < PTS; ++t) {
       const int k = tpc + t * TPC;
-      const cd xa = wr_shfl(X[(PTS - t) % PTS], pl), xb = wr_shfl(X[PTS - 1 - t], pl);
+      const cd xa = shfl_cd(X[(PTS - t) % PTS], pl), xb = shfl_cd(X[PTS - 1 - t], pl);
       const cd xm = tpc == 0 ? (t == 0 ? xn : xa) : xb;  // X[M - k]
       const cd e = make_cd(0.5 * (X[t].x + xm.x), 0.5 * (X[t].y - xm.y));
       const cd d = make_cd(0.5 * (X[t].x - xm.x), 0.5 * (X[t].y + xm.y));
@@ -225,12 +222,6 @@ hipError_t launch_wrx(int C, int M, int es, bool inv, const double* in, cd* H, c
 
 using namespace cfp;
 
-#define HIPCHK(expr)                                        \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return cfp::hip_error(_e, #expr); \
-  } while (0)
-
 struct cfp_wave_rplan_s {
   int device = 0;
   i64 n[3] = {1, 1, 1};
@@ -239,8 +230,8 @@ struct cfp_wave_rplan_s {
   int ncomp = 4;
   cd* H = nullptr;    // [ny nz][M][ncomp]
   cd* Q = nullptr;    // [ny nz][ncomp]
-  cd* twn = nullptr;  // W_nx
-  std::map<int, cd*> tw;  // W_ny, W_nz
+  TwiddleCache tw;
+  cd* twa[3] = {nullptr, nullptr, nullptr};  // tw's W_nx, W_ny, W_nz
   double2* tab[3] = {nullptr, nullptr, nullptr};  // x: kx = 0 .. M (M + 1 entries); y; z
   bool has_sym = false;
   double c0 = 0.0;
@@ -252,42 +243,18 @@ namespace {
 void free_wrplan(cfp_wave_rplan_s* p) {
   if (p->H) hipFree(p->H);
   if (p->Q) hipFree(p->Q);
-  if (p->twn) hipFree(p->twn);
-  for (auto& kv : p->tw) hipFree(kv.second);
+  p->tw.clear();
   for (int a = 0; a < 3; ++a)
     if (p->tab[a]) hipFree(p->tab[a]);
   delete p;
 }
 
-int upload_tw(cd** d, int n) {
-  const std::vector<cd> h = host_twiddles(n, -1);
-  HIPCHK(hipMalloc(d, sizeof(cd) * (size_t)n));
-  HIPCHK(hipMemcpy(*d, h.data(), sizeof(cd) * (size_t)n, hipMemcpyHostToDevice));
-  return CFP_SUCCESS;
-}
-
-// the pass over `axis` (1 or 2) of H (field 0: the grid M x ny x nz) or Q (field 1: 1 x ny x nz):
-// cfp_wave.hip's wave_pass on that grid, the x table starting at kx = 0 or at kx = M
+// the pass over `axis` (1 or 2) of H (field 0: the grid M x ny x nz) or Q (field 1: 1 x ny x nz),
+// the x table starting at kx = 0 or at kx = M
 PassDesc field_pass(const cfp_wave_rplan_s* p, int field, int axis, int mode) {
-  const i64 g0 = field ? 1 : p->M;
-  const i64 m[3] = {p->ncomp * g0, p->n[1], p->n[2]};
-  PassDesc d;
-  d.n = (int)p->n[axis];
-  d.in = d.out = natural_side(axis, m);
-  natural_cols(axis, m, &d.ncols, &d.inner_n);
-  d.mode = mode;
-  d.scale = 1.0;
-  d.colsym = d.axsym = d.diag = nullptr;
-  d.wave.tab[0] = field ? p->tab[0] + p->M : p->tab[0];
-  d.wave.tab[1] = p->tab[1];
-  d.wave.tab[2] = p->tab[2];
-  d.wave.n[0] = g0;
-  d.wave.n[1] = p->n[1];
-  d.wave.n[2] = p->n[2];
-  d.wave.c0sq = p->c0 * p->c0;
-  d.wave.fused = wave_real::fused_axis(p->n[1], p->n[2]);
-  d.wave.ncomp = p->ncomp;
-  return d;
+  const double2* const tab[3] = {field ? p->tab[0] + p->M : p->tab[0], p->tab[1], p->tab[2]};
+  return wave_field_pass(p->ncomp, field ? 1 : p->M, p->n[1], p->n[2], tab, p->c0,
+                         wave_real::fused_axis(p->n[1], p->n[2]), axis, mode, 1.0);
 }
 
 int run_wave_real(cfp_wave_rplan_s* p, const double* b, double* x, int es, hipStream_t s,
@@ -303,10 +270,10 @@ int run_wave_real(cfp_wave_rplan_s* p, const double* b, double* x, int es, hipSt
     hipError_t e;
     if (q.kind == wave_real::AXIS) {
       cd* f = q.field ? p->Q : p->H;
-      e = launch_axis_pass(field_pass(p, q.field, q.axis, q.mode), f, f, p->tw[(int)p->n[q.axis]], s);
+      e = launch_axis_pass(field_pass(p, q.field, q.axis, q.mode), f, f, p->twa[q.axis], s);
     } else {
       const bool inv = q.kind == wave_real::C2R;
-      e = launch_wrx(p->ncomp, (int)p->M, es, inv, b, p->H, p->Q, x, p->twn, rows, inv ? sc : 1.0, s);
+      e = launch_wrx(p->ncomp, (int)p->M, es, inv, b, p->H, p->Q, x, p->twa[0], rows, inv ? sc : 1.0, s);
     }
     if (e != hipSuccess) return hip_error(e, q.kind == wave_real::AXIS ? "real wave plan: axis pass" : "real wave plan: row sweep");
   }
@@ -326,9 +293,7 @@ extern "C" int cfp_wave_rplan_create(cfp_wave_rplan_t* plan, int64_t nx, int64_t
   *plan = nullptr;
   if (const char* why = wave_real::refusal(nx, ny, nz, dim))
     return set_error(CFP_ERR_SUP, why, (long long)nx, (long long)ny, (long long)nz, dim);
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return set_error(CFP_ERR_ARG_OUTOFRANGE, "device %d out of range", device);
+  CFPCHK(check_device(device));
   DeviceGuard g(device);
   cfp_wave_rplan_s* p = new cfp_wave_rplan_s;
   p->device = device;
@@ -343,9 +308,7 @@ extern "C" int cfp_wave_rplan_create(cfp_wave_rplan_t* plan, int64_t nx, int64_t
   hipError_t e = hipMalloc(&p->H, sizeof(cd) * rows * (size_t)p->M * p->ncomp);
   if (e == hipSuccess) e = hipMalloc(&p->Q, sizeof(cd) * rows * p->ncomp);
   int rc = e == hipSuccess ? CFP_SUCCESS : hip_error(e, "real wave plan buffers");
-  if (!rc) rc = upload_tw(&p->twn, (int)nx);
-  for (int a = 1; a < 3 && !rc; ++a)
-    if (!p->tw.count((int)p->n[a])) rc = upload_tw(&p->tw[(int)p->n[a]], (int)p->n[a]);
+  for (int a = 0; a < 3 && !rc; ++a) rc = p->tw.get((int)p->n[a], &p->twa[a]);
   if (rc) {
     free_wrplan(p);
     return rc;
@@ -363,13 +326,11 @@ extern "C" int cfp_wave_rplan_destroy(cfp_wave_rplan_t p) {
 
 extern "C" int cfp_wave_rplan_set_symbol(cfp_wave_rplan_t p, const double kappa[3], double c0) {
   if (!p || !kappa) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  if (!(c0 > 0.0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "c0 must be > 0");
-  for (int a = 0; a < 3; ++a)
-    if (!(kappa[a] >= 0.0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "kappa must be >= 0");
+  if (const char* why = wave::symbol_refusal(kappa, c0)) return set_error(CFP_ERR_ARG_OUTOFRANGE, "%s", why);
   DeviceGuard g(p->device);
   for (int a = 0; a < 3; ++a) {
     const std::vector<double> t =
-        a == 0 ? wave_real::x_table(p->n[0], kappa[0], c0) : wave_real::axis_table(p->n[a], p->n[a], kappa[a], c0);
+        a == 0 ? wave_real::x_table(p->n[0], kappa[0], c0) : wave::axis_table(p->n[a], p->n[a], kappa[a], c0, true);
     static_assert(sizeof(double2) == 2 * sizeof(double), "(p, q) pairs");
     if (!p->tab[a]) HIPCHK(hipMalloc(&p->tab[a], sizeof(double) * t.size()));
     HIPCHK(hipMemcpy(p->tab[a], t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
@@ -398,30 +359,8 @@ extern "C" int cfp_wave_rplan_num_passes(cfp_wave_rplan_t p, int* passes) {
 extern "C" int cfp_wave_rplan_time_passes(cfp_wave_rplan_t p, const double* b, double* x, int es, int iters,
                                           double* ms_out, void* stream) {
   if (!p || !b || !x || !ms_out) return set_error(CFP_ERR_ARG_NULL, "NULL argument");
-  if (iters < 1) return set_error(CFP_ERR_ARG_OUTOFRANGE, "iters must be >= 1");
   DeviceGuard g(p->device);
-  hipStream_t s = (hipStream_t)stream;
-  const size_t np = p->steps.size();
-  std::vector<double> acc(np, 0.0);
-  std::vector<hipEvent_t> ev(np + 1);
-  for (auto& e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  int rc = CFP_SUCCESS;
-  for (int it = 0; it < iters && rc == CFP_SUCCESS; ++it) {
-    rc = run_wave_real(p, b, x, es, s, &ev);
-    if (rc) break;
-    hipError_t e = hipEventSynchronize(ev[np]);
-    if (e != hipSuccess) {
-      rc = hip_error(e, "event sync");
-      break;
-    }
-    for (size_t i = 0; i < np; ++i) {
-      float ms = 0.f;
-      hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-      acc[i] += ms;
-    }
-  }
-  for (auto& e : ev) hipEventDestroy(e);
-  if (rc) return rc;
-  for (size_t i = 0; i < np; ++i) ms_out[i] = acc[i] / iters;
-  return CFP_SUCCESS;
+  return time_passes(p->steps.size(), false, iters, [&](std::vector<hipEvent_t>* ev) {
+    return run_wave_real(p, b, x, es, (hipStream_t)stream, ev);
+  }, ms_out);
 }

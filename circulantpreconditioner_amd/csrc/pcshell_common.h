@@ -1,9 +1,10 @@
 // pcshell_common.h -- helpers shared by the PCSHELL implementations (pcshell_boundary.cpp,
 // pcshell_fft3d.cpp, pcshell_fft3d_real.cpp, wave_system.cpp): cfp error -> PETSc error, device
 // views of Vecs (device arrays used in place, host arrays staged through a temporary device
-// buffer), slab plans on a communicator, and -- for the transport PCSHELL only -- the part of an
-// FFT matrix that both scalar builds share and the interface between the scalar-independent
-// boundary (pcshell_boundary.cpp) and the scalar build behind it.
+// buffer; apply_on_device: one PCApply on such views), slab plans on a communicator, and -- for
+// the transport PCSHELL only -- the part of an FFT matrix that both scalar builds share and the
+// interface between the scalar-independent boundary (pcshell_boundary.cpp) and the scalar build
+// behind it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -99,6 +100,27 @@ struct DevOut {
     return VecRestoreArrayWriteAndMemType(v, &arr);
   }
 };
+
+// One PCApply on the device views of b and x (n entries each): run(b, x, stream, staged) queues
+// the work.  Device Vecs are ordered on the Vec stream without a host round trip (device_stream);
+// with a staged host Vec (staged: the default stream) the work is waited for, since put() copies
+// the buffers back and frees them.  `where` names the caller in the error.
+template <class Run>
+PetscErrorCode apply_on_device(Vec b, Vec x, PetscInt n, const char* where, Run run) {
+  DevIn in;
+  DevOut out;
+  PetscCall(in.get(b, n));
+  PetscCall(out.get(x, n));
+  const bool staged = in.tmp || out.tmp;
+  void* st = nullptr;
+  bool wait = true;
+  if (!staged) device_stream(&st, &wait);
+  int rc = run(in.ptr(), out.ptr(), st, staged);
+  if (rc == CFP_SUCCESS && (wait || staged)) rc = cfp_stream_sync(st);
+  PetscCall(out.put());
+  PetscCall(in.put());
+  return cfp_err(rc, where);
+}
 
 // ------------------------------------------------------------------ slab plans on a communicator
 // The z-slab plan behind an FFT matrix of several ranks (the complex build, pcshell_fft3d.cpp, and

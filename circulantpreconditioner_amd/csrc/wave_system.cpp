@@ -22,6 +22,7 @@
 #include "../../include/transport_equation.h"
 #include "../../include/wave_system.h"
 #include "cfp_fft_device.h"
+#include "cfp_wave_host.h"
 #include "pcshell_common.h"
 
 using namespace cfp_pc;
@@ -335,18 +336,16 @@ PetscErrorCode wave_dist_setup(FFTPrecWaveContext* ctx, int P, int dev) {
   if (!e) e = cfp_err(cfp_slab_layout(w->pd[0], w->pd[1], w->pd[2], P, rank, lay), "setupFFTPrec3DWave");
   w->nloc = lay[4];
   w->z0 = lay[2];
-  // the symbol's per-axis (p, q) = (kappa c0 (1 - cos theta), kappa sin theta), as cfp_wave_plan_set_symbol
+  // the symbol's per-axis (p, q) tables, cfp_wave_plan_set_symbol's, one after the other
   const int64_t n3[3] = {ctx->n_x, ctx->n_y, ctx->n_z};
   const double kap[3] = {ctx->kappa_x, ctx->kappa_y, ctx->kappa_z};
-  std::vector<double2> t;
-  for (int a = 0; a < 3; ++a)
-    for (int64_t k = 0; k < n3[a]; ++k) {
-      const long double th = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n3[a];
-      t.push_back(make_double2((double)((long double)kap[a] * ctx->c0 * (1.0L - cosl(th))),
-                               (double)((long double)kap[a] * sinl(th))));
-    }
-  if (!e && (hipMalloc(&w->tab, sizeof(double2) * t.size()) != hipSuccess ||
-             hipMemcpy(w->tab, t.data(), sizeof(double2) * t.size(), hipMemcpyHostToDevice) != hipSuccess ||
+  std::vector<double> t;
+  for (int a = 0; a < 3; ++a) {
+    const std::vector<double> ta = cfp::wave::axis_table(n3[a], n3[a], kap[a], ctx->c0, false);
+    t.insert(t.end(), ta.begin(), ta.end());
+  }
+  if (!e && (hipMalloc(&w->tab, sizeof(double) * t.size()) != hipSuccess ||
+             hipMemcpy(w->tab, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice) != hipSuccess ||
              hipMalloc(&w->buf, sizeof(cfp::cd) * 2 * w->ncomp * (size_t)(w->nloc > 0 ? w->nloc : 1)) != hipSuccess))
     e = PetscErrorSet(PETSC_ERR_MEM, "setupFFTPrec3DWave", "slab buffers");
   w->c0sq = ctx->c0 * ctx->c0;
@@ -445,37 +444,21 @@ extern "C" PetscErrorCode applyFFT3DPrecWave(PC pc, Vec b, Vec x) {
   const PetscInt M = ((ctx->dim ? ctx->dim : 3) + 1) * ctx->n_x * ctx->n_y * ctx->n_z;
   PetscCall(check_size(b, M, "applyFFT3DPrecWave: b has the wrong size"));
   PetscCall(check_size(x, M, "applyFFT3DPrecWave: x has the wrong size"));
-  DevIn in;
-  DevOut out;
-  PetscCall(in.get(b, M));
-  PetscCall(out.get(x, M));
-  // device Vecs: ordered on the Vec stream without a host round trip (cfp_pc::device_stream);
-  // a staged host Vec is waited for (its buffers are copied back / freed below)
-  void* st = nullptr;
-  bool wait = true;
-  if (!in.tmp && !out.tmp) device_stream(&st, &wait);
-  // the stand-in KSP may ask for dots of x with its basis (PCMiniApplyDots): on the 3-sweep
-  // schedule they ride in the last sweep's stores (cfp_wave_plan_apply_dots); otherwise the
-  // request stays open and the KSP runs its own multi-dot
-  PCMiniApplyDots* req = nullptr;
-  int npass = 0;
-  if (!in.tmp && !out.tmp && PCMiniGetApplyDots(pc, &req) == PETSC_SUCCESS && req && !req->done && req->nv >= 1 &&
-      req->nv <= 4 && cfp_wave_plan_num_passes(ctx->plan, &npass) == CFP_SUCCESS && npass == 3) {
+  PetscCall(apply_on_device(b, x, M, __func__, [&](const double* bp, double* xp, void* st, bool staged) {
+    // the stand-in KSP may ask for dots of x with its basis (PCMiniApplyDots): on the 3-sweep
+    // schedule they ride in the last sweep's stores (cfp_wave_plan_apply_dots); otherwise the
+    // request stays open and the KSP runs its own multi-dot
+    PCMiniApplyDots* req = nullptr;
+    int npass = 0;
+    if (staged || PCMiniGetApplyDots(pc, &req) != PETSC_SUCCESS || !req || req->done || req->nv < 1 || req->nv > 4 ||
+        cfp_wave_plan_num_passes(ctx->plan, &npass) != CFP_SUCCESS || npass != 3)
+      return cfp_wave_plan_apply(ctx->plan, bp, xp, st);
     int fused = 0;
-    int rc = cfp_wave_plan_apply_dots(ctx->plan, in.ptr(), out.ptr(), st, (int)req->nv,
-                                      reinterpret_cast<const double* const*>(req->v), req->out, &fused);
+    const int rc = cfp_wave_plan_apply_dots(ctx->plan, bp, xp, st, (int)req->nv,
+                                            reinterpret_cast<const double* const*>(req->v), req->out, &fused);
     if (rc == CFP_SUCCESS && fused) req->done = PETSC_TRUE;
-    if (rc == CFP_SUCCESS && wait) rc = cfp_stream_sync(st);
-    PetscCall(out.put());
-    PetscCall(in.put());
-    CFPCALL(rc);
-    PetscFunctionReturn(PETSC_SUCCESS);
-  }
-  int rc = cfp_wave_plan_apply(ctx->plan, in.ptr(), out.ptr(), st);
-  if (rc == CFP_SUCCESS && (wait || in.tmp || out.tmp)) rc = cfp_stream_sync(st);
-  PetscCall(out.put());
-  PetscCall(in.put());
-  CFPCALL(rc);
+    return rc;
+  }));
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 

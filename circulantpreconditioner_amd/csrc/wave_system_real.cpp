@@ -5,7 +5,7 @@
 // arrays: PetscScalar = double reads and writes the (dim+1) N reals themselves (es = 1);
 // PetscScalar complex reads the real parts and writes a zero imaginary part (es = 2), which is
 // exact wherever the data are real (GMRES on the real wave operator with a real right-hand side).
-// Host and device Vecs are handled as applyFFT3DPrecWave handles them (wave_system.cpp).
+// Host and device Vecs are handled as applyFFT3DPrecWave handles them (apply_on_device).
 #include "../../include/circulant_fft.h"
 #include "../../include/wave_system_real.h"
 #include "pcshell_common.h"
@@ -52,20 +52,9 @@ extern "C" PetscErrorCode applyFFT3DPrecWaveRealData(PC pc, Vec b, Vec x) {
   const PetscInt M = (ctx_dim(ctx) + 1) * ctx->n_x * ctx->n_y * ctx->n_z;
   PetscCall(check_size(b, M, "applyFFT3DPrecWaveRealData: b has the wrong size"));
   PetscCall(check_size(x, M, "applyFFT3DPrecWaveRealData: x has the wrong size"));
-  DevIn in;
-  DevOut out;
-  PetscCall(in.get(b, M));
-  PetscCall(out.get(x, M));
-  // device Vecs: ordered on the Vec stream without a host round trip (cfp_pc::device_stream);
-  // a staged host Vec is waited for (its buffers are copied back / freed below)
-  void* st = nullptr;
-  bool wait = true;
-  if (!in.tmp && !out.tmp) device_stream(&st, &wait);
-  int rc = cfp_wave_rplan_apply_strided(ctx->plan, in.ptr(), out.ptr(), kEs, st);
-  if (rc == CFP_SUCCESS && (wait || in.tmp || out.tmp)) rc = cfp_stream_sync(st);
-  PetscCall(out.put());
-  PetscCall(in.put());
-  CFPCALL(rc);
+  PetscCall(apply_on_device(b, x, M, __func__, [&](const double* bp, double* xp, void* st, bool) {
+    return cfp_wave_rplan_apply_strided(ctx->plan, bp, xp, kEs, st);
+  }));
   PetscFunctionReturn(PETSC_SUCCESS);
 }
 

@@ -39,8 +39,11 @@ def _dims3(dims: Sequence[int]) -> tuple:
     return d + (1,) * (3 - len(d))
 
 
-class WavePlan:
-    """Block-circulant inverse on an nx*ny*nz grid with dim + 1 interleaved components."""
+class _WaveHandle:
+    """What the two wave plans share: the grid, the life of the C plan behind ``_h`` and the
+    entries every wave plan has under its prefix (set_symbol, num_passes, time_passes, destroy)."""
+
+    _CREATE = _PREFIX = ""
 
     def __init__(self, dims: Sequence[int], device: int | None = None, dim: int = 3):
         nx, ny, nz = _dims3(dims)
@@ -48,14 +51,49 @@ class WavePlan:
         self.dim = int(dim)
         self.ncomp = self.dim + 1
         self.size = self.ncomp * nx * ny * nz
+        self._h = None
         self.device = torch.cuda.current_device() if device is None else int(device)
         h = ctypes.c_void_p()
-        check(lib().cfp_wave_plan_create_dim(ctypes.byref(h), nx, ny, nz, self.dim, self.device))
+        check(getattr(lib(), self._CREATE)(ctypes.byref(h), nx, ny, nz, self.dim, self.device))
         self._h = h
 
-    def set_symbol(self, kappa: Sequence[float], c0: float = C0) -> "WavePlan":
-        check(lib().cfp_wave_plan_set_symbol(self._h, _d3(kappa), float(c0)))
+    def _fn(self, name: str):
+        return getattr(lib(), f"{self._PREFIX}_{name}")
+
+    def set_symbol(self, kappa: Sequence[float], c0: float = C0):
+        check(self._fn("set_symbol")(self._h, _d3(kappa), float(c0)))
         return self
+
+    def num_passes(self) -> int:
+        n = ctypes.c_int()
+        check(self._fn("num_passes")(self._h, ctypes.byref(n)))
+        return n.value
+
+    def time_passes(self, b: torch.Tensor, x: torch.Tensor, iters: int = 10, stream=None) -> list:
+        """Mean device ms of each launch of the schedule (events between them)."""
+        ms = (ctypes.c_double * self.num_passes())()
+        check(self._fn("time_passes")(self._h, *self._timed_args(b, x), int(iters), ms, _stream_handle(stream)))
+        return list(ms)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WavePlan(_WaveHandle):
+    """Block-circulant inverse on an nx*ny*nz grid with dim + 1 interleaved components."""
+
+    _CREATE, _PREFIX = "cfp_wave_plan_create_dim", "cfp_wave_plan"
+
+    def _timed_args(self, b, x) -> tuple:
+        return _dev_ptr(b, self.size, "b"), _dev_ptr(x, self.size, "x")
 
     SCHEDULES = {"auto": 0, "five": 1, "three": 2}
 
@@ -100,29 +138,6 @@ class WavePlan:
                                            _stream_handle(stream)))
         return out
 
-    def num_passes(self) -> int:
-        n = ctypes.c_int()
-        check(lib().cfp_wave_plan_num_passes(self._h, ctypes.byref(n)))
-        return n.value
-
-    def time_passes(self, b: torch.Tensor, x: torch.Tensor, iters: int = 10, stream=None) -> list:
-        np_ = self.num_passes()
-        ms = (ctypes.c_double * np_)()
-        check(lib().cfp_wave_plan_time_passes(self._h, _dev_ptr(b, self.size, "b"), _dev_ptr(x, self.size, "x"),
-                                              int(iters), ms, _stream_handle(stream)))
-        return list(ms)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cfp_wave_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def real_plan_supported(dims: Sequence[int], dim: int = 3) -> bool:
     """cfp_wave_rplan_supported: whether RealWavePlan serves the grid (host arithmetic, no device)."""
@@ -130,27 +145,17 @@ def real_plan_supported(dims: Sequence[int], dim: int = 3) -> bool:
     return bool(lib().cfp_wave_rplan_supported(nx, ny, nz, int(dim)))
 
 
-class RealWavePlan:
+class RealWavePlan(_WaveHandle):
     """x = S^{-1} b for real b on an nx*ny*nz grid with dim + 1 interleaved components, on the half
     spectrum kx <= nx/2: dim = 3, or dim = 2 with nz = 1; nx/2 a power of two in [16, 512]
     (``real_plan_supported``; anything else raises).  Half the memory traffic of ``WavePlan``'s
     five passes."""
 
-    def __init__(self, dims: Sequence[int], device: int | None = None, dim: int = 3):
-        nx, ny, nz = _dims3(dims)
-        self.dims = (nx, ny, nz)
-        self.dim = int(dim)
-        self.ncomp = self.dim + 1
-        self.size = self.ncomp * nx * ny * nz
-        self._h = None
-        self.device = torch.cuda.current_device() if device is None else int(device)
-        h = ctypes.c_void_p()
-        check(lib().cfp_wave_rplan_create(ctypes.byref(h), nx, ny, nz, self.dim, self.device))
-        self._h = h
+    _CREATE, _PREFIX = "cfp_wave_rplan_create", "cfp_wave_rplan"
 
-    def set_symbol(self, kappa: Sequence[float], c0: float = C0) -> "RealWavePlan":
-        check(lib().cfp_wave_rplan_set_symbol(self._h, _d3(kappa), float(c0)))
-        return self
+    def _timed_args(self, b, x) -> tuple:
+        es = 2 if b.dtype == torch.complex128 else 1
+        return self._ptr(b, "b"), self._ptr(x, "x"), es
 
     def _ptr(self, t: torch.Tensor, name: str) -> int:
         if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float64, torch.complex128):
@@ -173,30 +178,6 @@ class RealWavePlan:
         check(lib().cfp_wave_rplan_apply_strided(self._h, self._ptr(b, "b"), self._ptr(out, "out"), es,
                                                  _stream_handle(stream)))
         return out
-
-    def num_passes(self) -> int:
-        n = ctypes.c_int()
-        check(lib().cfp_wave_rplan_num_passes(self._h, ctypes.byref(n)))
-        return n.value
-
-    def time_passes(self, b: torch.Tensor, x: torch.Tensor, iters: int = 10, stream=None) -> list:
-        """Mean device ms of each launch of the schedule (events between them)."""
-        ms = (ctypes.c_double * self.num_passes())()
-        es = 2 if b.dtype == torch.complex128 else 1
-        check(lib().cfp_wave_rplan_time_passes(self._h, self._ptr(b, "b"), self._ptr(x, "x"), es, int(iters), ms,
-                                               _stream_handle(stream)))
-        return list(ms)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cfp_wave_rplan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def wave_csr(dims: Sequence[int], h: Sequence[float], dt: float, c0: float = C0, bc: str | int = "wall",

@@ -1,5 +1,5 @@
-// wave_real_host_check.cpp -- the host arithmetic of the real-data wave plan
-// (circulantpreconditioner_amd/csrc/cfp_wave_real_host.h) in a stand-alone program, meant to be
+// wave_real_host_check.cpp -- the host arithmetic of the wave family
+// (circulantpreconditioner_amd/csrc/cfp_wave_host.h) in a stand-alone program, meant to be
 // built with a host sanitizer and run on the CPU:
 //
 //   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
@@ -7,12 +7,13 @@
 //   ./wave_real_host_check
 //
 // It checks the supported-grid predicate on a sweep, the schedule of every kind of grid and the
-// symbol tables (sizes, end values, the exact zeros the Nyquist field relies on).  Exit 0 = ok.
+// symbol tables (sizes, end values, the exact zeros the Nyquist field relies on, and that the
+// shared table's two rules differ in nothing else).  Exit 0 = ok.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
-#include "cfp_wave_real_host.h"
+#include "cfp_wave_host.h"
 
 using namespace cfp::wave_real;
 
@@ -90,12 +91,27 @@ int main() {
     }
   }
   for (int64_t n : {1, 3, 5, 12, 20}) {
-    const std::vector<double> t = axis_table(n, n, kappa, c0);
+    const std::vector<double> t = cfp::wave::axis_table(n, n, kappa, c0, true);
     CHECK((int64_t)t.size() == 2 * n && t[0] == 0.0 && t[1] == 0.0);
     for (int64_t k = 1; k < n; ++k)  // q(-k) = -q(k), p(-k) = p(k): the symbol is Hermitian
       CHECK(std::fabs(t[(size_t)(2 * k + 1)] + t[(size_t)(2 * (n - k) + 1)]) <= 1e-15 &&
             std::fabs(t[(size_t)(2 * k)] - t[(size_t)(2 * (n - k))]) <= 1e-12 * kappa * c0);
   }
+  // the shared table: the complex plan's rule (flag off) and the real-data plan's (flag on) agree
+  // bit for bit except q at the self-mirrored k = 0 and 2 k = n, which the flag makes exactly 0
+  for (int64_t n : {1, 2, 5, 32, 50, 1024}) {
+    const std::vector<double> off = cfp::wave::axis_table(n, n, kappa, c0, false),
+                              on = cfp::wave::axis_table(n, n, kappa, c0, true);
+    CHECK(off.size() == on.size() && (int64_t)on.size() == 2 * n);
+    for (int64_t k = 0; k < n; ++k) {
+      CHECK(off[(size_t)(2 * k)] == on[(size_t)(2 * k)]);  // p never differs
+      if (k == 0 || 2 * k == n) CHECK(on[(size_t)(2 * k + 1)] == 0.0);
+      else CHECK(off[(size_t)(2 * k + 1)] == on[(size_t)(2 * k + 1)]);
+    }
+  }
+  const double bad[3] = {0.1, -1.0, 0.0}, good[3] = {0.1, 0.0, 0.2};
+  CHECK(cfp::wave::symbol_refusal(good, c0) == nullptr && cfp::wave::symbol_refusal(good, 0.0) != nullptr &&
+        cfp::wave::symbol_refusal(bad, c0) != nullptr);
   std::printf(fails ? "wave_real_host_check: %d check(s) failed\n" : "wave_real_host_check: ok (%d grids accepted)\n",
               fails ? fails : accepted);
   return fails ? 1 : 0;
